@@ -2,6 +2,20 @@
 dropout 0.1, label-smoothed CE, AdamW) — BASELINE.json configs[2] — on 1..8 MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config vit_base_224|latent_vit|image_vit_48|...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up, W warm-up steps, the
+K timed steps, the outputs of the last timed step to DIR if --dump-outputs is given, one JSON
+line (images/s, ms_per_step, per-step percentiles, step_mfma_frac). --full adds what takes runs
+of its own: the rocprofv3 traffic passes, the roofline probe phases and the CPU baselines
+described below (`roofline`, `cpu_baseline`, `cpu_baseline_cfg1` in the JSON line).
+
+--dump-outputs DIR: what a caller of the timed step receives from its last timed step, as float32
+`DIR/<name>.npy`: `loss` (the step's return value), `logits` (the forward output the loss was
+taken of) and, per parameter the optimizer updated, `param.<name>`: the values after that step at
+up to 65536 positions drawn once with a fixed seed (all of them for smaller parameters). Model
+init, inputs and dropout seeds are fixed, so two builds run with the same arguments see the same
+inputs.
 
 --gpus N > 1 without a torch.distributed environment: this process starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a CHILD (it never touches
@@ -15,7 +29,7 @@ that time); one HIP event per step boundary gives the per-step median / p10 / p9
 
 roofline: the dominant kernel is `gemm_8ph_kernel`, the bf16 MFMA GEMM of every forward and
 input-gradient linear (QKV, out-proj, fc1, fc2, patch embed; ~55 % of the step). Its launches
-are timed in a separate PROBE phase after the timed region (HIP events on the launch stream
+are timed (--full) in a separate PROBE phase after the timed region (HIP events on the launch stream
 around each launch, so the timed region carries no probe events; weight gradients on the compute
 stream during the probe, so no launch shares the chip with a concurrent one): achieved = sum over one
 step's 8-phase launches of 2*M*N*K / sum of their durations, vs the dense bf16 MFMA peak
@@ -24,7 +38,7 @@ step's 8-phase launches of 2*M*N*K / sum of their durations, vs the dense bf16 M
 WRITE_SIZE; one counter per pass, child processes run before this process touches the GPU).
 `step_mfma_frac` is the whole step's algorithmic GEMM+attention FLOPs (SURVEY §8d:
 105.38 GFLOP/img fwd+bwd) / step time / peak.
-cpu_baseline: the CPU oracle (oracle/vit_oracle.py, same model, fp32, dropout 0.1, AdamW)
+cpu_baseline (--full): the CPU oracle (oracle/vit_oracle.py, same model, fp32, dropout 0.1, AdamW)
 timed on the host cores for a bounded sample (rank 0, N=1 only); cpu_baseline_cfg1 the same
 for BASELINE configs[0] (48 px ImageViT d6/h8, bs=64, the reference's CPU-runnable case).
 """
@@ -339,6 +353,30 @@ def spawn_ranks(args) -> int:
     return r.returncode
 
 
+DUMP_SAMPLE = 65536  # positions kept of each parameter (ViT-B/16: 152 parameters, about 12 MB in all)
+
+
+def dump_outputs(dirname, loss, logits, model):
+    """--dump-outputs: the last timed step's loss, logits and updated parameters (module
+    docstring) as float32 .npy files. Sample positions come from one CPU generator with a fixed
+    seed walked over the parameters in registration order, so they depend on the shapes alone."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1), "logits": logits.detach().float()}
+    g = torch.Generator().manual_seed(20240607)
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays["param." + name] = flat.float()
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
+
+
 def percentile(xs, q):
     xs = sorted(xs)
     if not xs:
@@ -353,11 +391,15 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="vit_base_224", choices=list(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC traffic passes")
-    ap.add_argument("--probe-steps", type=int, default=2, help="steps of the (untimed) roofline probe phase")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, logits and (sampled) updated parameters to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the rocprofv3 traffic passes, the roofline probe phases and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the rocprofv3 PMC traffic passes")
+    ap.add_argument("--probe-steps", type=int, default=2, help="--full: steps of the (untimed) roofline probe phase")
     ap.add_argument("--probe-all", action="store_true",
-                    help="probe phase: time every other GEMM launch too (stderr table, not the JSON line)")
+                    help="--full probe phase: time every other GEMM launch too (stderr table, not the JSON line)")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the whole step as a HIP graph (auto: on for the launch-bound small configs)")
     ap.add_argument("--grad-dtype", choices=["fp32", "bf16"], default="fp32",
@@ -365,6 +407,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch plumbing only (gloo, CPU): ranks rendezvous, barrier, rank 0 prints the JSON line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
@@ -387,7 +431,7 @@ def main():
         return
 
     traffic, traffic_detail = None, "not measured (N>1, --no-traffic or not the ViT-B/16 config)"
-    if world == 1 and not args.no_traffic and args.config == "vit_base_224":
+    if args.full and world == 1 and not args.no_traffic and args.config == "vit_base_224":
         # child rocprofv3 passes first: this process has not initialised the GPU yet
         traffic, traffic_detail = pmc_traffic()
     torch.cuda.set_device(local)
@@ -431,11 +475,15 @@ def main():
         adapters = L * 2 * N * (2 * D * 64)
         flops_img = 2 * trunk + 3 * (adapters + 2 * 18 * 512 * D + 2 * D * 7)
     probe = GemmProbe(args.probe_all)
-    ops.LAUNCH_PROBE = probe
+    if args.full:
+        ops.LAUNCH_PROBE = probe
+    last = {}  # the forward output of the latest step (under graph replay: the captured step's buffer)
 
     def step():
         opt.zero_grad()
-        loss = crit(net(x), y)
+        logits = net(x)
+        last["logits"] = logits.detach()
+        loss = crit(logits, y)
         loss.backward()
         opt.step()
         return loss
@@ -470,39 +518,59 @@ def main():
         el = t.item()
     step_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)]
     lossv = loss.item()
-    # probe phases (untimed): HIP events around every gemm_8ph launch of a few eager steps.
-    # In-step: as the timed steps run them (weight-gradient stream on, so a launch may share the chip
-    # with a concurrent split-K weight gradient); isolated (the roofline `frac`): weight-gradient
-    # stream off, every launch alone on the chip.
+    if args.dump_outputs and rank == 0:  # before the graph (whose pool holds its step's outputs) goes
+        dump_outputs(args.dump_outputs, loss, last["logits"], model)
     if use_graph:
         graph.release()
-    probe.on = True
-    for _ in range(args.probe_steps):
-        step()
-    torch.cuda.synchronize()
-    ps_in = probe.summary(args.probe_steps)
-    probe.rec, probe.other = [], []
-    wg_on = runtime.WGRAD.enabled
-    runtime.WGRAD.enabled = False
-    for _ in range(args.probe_steps):
-        step()
-    torch.cuda.synchronize()
-    probe.on = False
-    runtime.WGRAD.enabled = wg_on
-    ps = probe.summary(args.probe_steps)
-    if probe.all and rank == 0:
-        print(probe.other_table(args.probe_steps), file=sys.stderr, flush=True)
     ms = el / args.steps * 1e3
     imgs = world * B * args.steps / el
     step_tflops = flops_img * B / (ms / 1e3) / 1e12
-    achieved = ps["flop_per_launch"] / (ps["mean_launch_ms"] / 1e3) / 1e12 if ps["launches"] else 0.0
-    achieved_in = ps_in["flop_per_launch"] / (ps_in["mean_launch_ms"] / 1e3) / 1e12 if ps_in["launches"] else 0.0
-    if rank == 0:
-        cpu = cpu1 = None
-        if world == 1 and not args.no_cpu_baseline:
+    roofline = cpu = cpu1 = None
+    if args.full:
+        # probe phases (untimed): HIP events around every gemm_8ph launch of a few eager steps.
+        # In-step: as the timed steps run them (weight-gradient stream on, so a launch may share the chip
+        # with a concurrent split-K weight gradient); isolated (the roofline `frac`): weight-gradient
+        # stream off, every launch alone on the chip.
+        probe.on = True
+        for _ in range(args.probe_steps):
+            step()
+        torch.cuda.synchronize()
+        ps_in = probe.summary(args.probe_steps)
+        probe.rec, probe.other = [], []
+        wg_on = runtime.WGRAD.enabled
+        runtime.WGRAD.enabled = False
+        for _ in range(args.probe_steps):
+            step()
+        torch.cuda.synchronize()
+        probe.on = False
+        runtime.WGRAD.enabled = wg_on
+        ps = probe.summary(args.probe_steps)
+        if probe.all and rank == 0:
+            print(probe.other_table(args.probe_steps), file=sys.stderr, flush=True)
+        achieved = ps["flop_per_launch"] / (ps["mean_launch_ms"] / 1e3) / 1e12 if ps["launches"] else 0.0
+        achieved_in = ps_in["flop_per_launch"] / (ps_in["mean_launch_ms"] / 1e3) / 1e12 if ps_in["launches"] else 0.0
+        roofline = {"bound": "mfma", "kernel": "gemm_8ph_kernel (bf16 MFMA; every fwd + dgrad linear and the "
+                                               "patch embed, fused epilogues)",
+                    "achieved": round(achieved, 1), "peak": round(PEAK_BF16_TFLOPS, 1), "unit": "TFLOP/s",
+                    "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                    "frac_in_step": round(achieved_in / PEAK_BF16_TFLOPS, 4),
+                    "mean_launch_ms_in_step": round(ps_in["mean_launch_ms"], 4),
+                    "frac_note": "frac: each launch alone on the chip (weight-gradient stream off); "
+                                 "frac_in_step: the same launches in eager train steps with the "
+                                 "weight-gradient stream on (sharing CUs with split-K weight gradients)",
+                    "traffic": None if traffic is None else round(traffic),
+                    "traffic_detail": traffic_detail,
+                    "algorithmic_bytes": round(ps["algo_bytes_per_launch"]),
+                    "flop_per_launch": round(ps["flop_per_launch"]),
+                    "launches_per_step": ps["launches_per_step"],
+                    "mean_launch_ms": round(ps["mean_launch_ms"], 4),
+                    "kernel_ms_per_step": round(ps["ms_per_step"], 3),
+                    "per_shape": ps["per_shape"]}
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.config)
             if args.config == "vit_base_224":
                 cpu1 = cpu_baseline("image_vit_48", bs=64)
+    if rank == 0:
         out = {
             "metric": METRIC, "value": round(imgs, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
@@ -511,32 +579,16 @@ def main():
                        "parallelism": f"dp{world}", "grad_allreduce": args.grad_dtype if world > 1 else None},
             "step_ms_median": round(percentile(step_ms, 0.5), 3), "step_ms_p10": round(percentile(step_ms, 0.1), 3),
             "step_ms_p90": round(percentile(step_ms, 0.9), 3),
-            "roofline": {"bound": "mfma", "kernel": "gemm_8ph_kernel (bf16 MFMA; every fwd + dgrad linear and the "
-                                                    "patch embed, fused epilogues)",
-                         "achieved": round(achieved, 1), "peak": round(PEAK_BF16_TFLOPS, 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                         "frac_in_step": round(achieved_in / PEAK_BF16_TFLOPS, 4),
-                         "mean_launch_ms_in_step": round(ps_in["mean_launch_ms"], 4),
-                         "frac_note": "frac: each launch alone on the chip (weight-gradient stream off); "
-                                      "frac_in_step: the same launches in eager train steps with the "
-                                      "weight-gradient stream on (sharing CUs with split-K weight gradients)",
-                         "traffic": None if traffic is None else round(traffic),
-                         "traffic_detail": traffic_detail,
-                         "algorithmic_bytes": round(ps["algo_bytes_per_launch"]),
-                         "flop_per_launch": round(ps["flop_per_launch"]),
-                         "launches_per_step": ps["launches_per_step"],
-                         "mean_launch_ms": round(ps["mean_launch_ms"], 4),
-                         "kernel_ms_per_step": round(ps["ms_per_step"], 3),
-                         "per_shape": ps["per_shape"]},
             "launch": "hipGraph replay of the whole step" if use_graph else "eager (one host launch per kernel)",
             "step_mfma_frac": round(step_tflops / PEAK_BF16_TFLOPS, 4),
             "step_tflops": round(step_tflops, 1),
             "final_loss": round(lossv, 4),
             "ranks_seen": dist.get_world_size() if world > 1 else 1,
             "rccl": rccl,
-            "cpu_baseline": cpu,
-            "cpu_baseline_cfg1": cpu1,
+            "full": args.full,
         }
+        if args.full:
+            out.update({"roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_cfg1": cpu1})
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

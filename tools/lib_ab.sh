@@ -26,7 +26,7 @@ for s in $STEPS; do
       done; done ;;
     bench)
       for rep in $(seq ${REPS:-3}); do for lib in $LIBS; do
-        FERVIT_LIB=$L/$lib timeout -k 10 300 python -u bench.py --config ${CFG:-vit_base_224} --steps ${BSTEPS:-30} --warmup 5 --no-cpu-baseline --no-traffic \
+        FERVIT_LIB=$L/$lib timeout -k 10 300 python -u bench.py --full --config ${CFG:-vit_base_224} --steps ${BSTEPS:-30} --warmup 5 --no-cpu-baseline --no-traffic \
           2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('[$lib]', d['ms_per_step'], d['step_ms_median'], (d.get('roofline') or {}).get('frac'), (d.get('roofline') or {}).get('frac_in_step'))" \
           | tee -a gpurun_out/${TAG}_bench_ab.txt || exit 1
       done; done ;;
