@@ -572,12 +572,14 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
     for (int c = 0; c < C; ++c) m = fmaxf(m, z[c]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(z[c] - m);
-    const float lse = m + logf(se);
+    // -log p_c = log(se) + (m - z_c): the difference first (exact for nearby logits), so the term keeps
+    // its own precision; (m + log(se)) - z_c rounds the sum to an ulp of |m| (5e-4 at logits ~1e4)
+    const float lg = logf(se);
     const int yb = (int)y[b];
     const float wy = wt ? wt[yb] : 1.f;
     float sm = 0.f;
-    for (int c = 0; c < C; ++c) sm += (wt ? wt[c] : 1.f) * (lse - z[c]);
-    num += (1.f - ls) * wy * (lse - z[yb]) + ls / C * sm;
+    for (int c = 0; c < C; ++c) sm += (wt ? wt[c] : 1.f) * (lg + (m - z[c]));
+    num += (1.f - ls) * wy * (lg + (m - z[yb])) + ls / C * sm;
     den += wy;
   }
   num = wave_sum(num);

@@ -131,8 +131,10 @@ int fer_layernorm_fwd(int dtype, const void* x, int64_t ldx, const float* gamma,
 /* LayerNorm backward. dx = LN'(dy) (+ res), optional dx_drop = dropout_bwd(dx) (mask of
  * the branch feeding the norm's input, post-norm residual `x + Drop(h)`).
  * Column partial sums go to ws ([nblk][3][D] fp32, ws_bytes >= fer_layernorm_bwd_ws(M,D));
- * dgamma/dbeta/dbias (optional, [gamma_rows][D] fp32) receive sum(dy*xhat), sum(dy),
- * sum(dx_drop or dx); accumulate != 0 adds to them. */
+ * dgamma/dbeta/dbias (optional, [D] fp32) receive sum(dy*xhat), sum(dy), sum(dx_drop or dx)
+ * over all rows; accumulate != 0 adds to them. They need a shared gamma: with gamma_rows > 1
+ * asking for any of them is an error ("parameter grads need shared gamma"; LayerWiseNorm's
+ * per-layer gradients come from fer_wplus_bwd). dx_drop has dx's row stride lddx. */
 int64_t fer_layernorm_bwd_ws(int M, int D);
 int fer_layernorm_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* mean,
                       const float* rstd, const float* gamma, int gamma_rows, int row_div, const void* res,
