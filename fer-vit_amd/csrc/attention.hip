@@ -143,10 +143,11 @@ FER_DEV void store_rows_q(bf16* o, const f32x16& a0, const f32x16& a1, float mul
 // ---------------------------------------------------------------- forward
 // One workgroup per (batch, head), wave w = query block w. K and V images arrive by LDS-DMA;
 // S^T = K Q^T per 32-key block with an online (running max) softmax, O^T += V^T P^T.
-template <int NB>
-__global__ __launch_bounds__(64 * NB) __attribute__((amdgpu_waves_per_eu(4))) void attn_fwd_bf16(const bf16* __restrict__ qkv, long ldq, bf16* __restrict__ out,
+// Runs 224 < N <= 256 only (eight query blocks; smaller N takes the persistent / occupancy kernels).
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void attn_fwd_bf16(const bf16* __restrict__ qkv, long ldq, bf16* __restrict__ out,
                                                           long ldo, float* __restrict__ lse, int N, int H, int dh,
                                                           float sl2, uint32_t thr, float dscale, uint64_t seed) {
+  constexpr int NB = 8;
   seed = step_seed(seed);
   __shared__ __attribute__((aligned(1024))) char lds[2 * NB * 32 * 128];
   char* Ki = lds;
@@ -810,14 +811,15 @@ FER_DEV bf16x8 rd_tr64b(const char* img, int2 b) {
 // dQacc: [NB*32 queries][64 d] fp32, 16-byte chunk index XOR (row & 15)
 FER_DEV int dq_off(int row, int chunk) { return row * 256 + ((chunk ^ (row & 15)) << 4); }
 
-template <int NB>
-__global__ __launch_bounds__(64 * NB) void attn_bwd_fused_bf16(const bf16* __restrict__ qkv, long ldq,
+// (224 < N <= 256 only: eight query blocks, as attn_fwd_bf16)
+__global__ __launch_bounds__(512) void attn_bwd_fused_bf16(const bf16* __restrict__ qkv, long ldq,
                                                                const bf16* __restrict__ out, long ldo,
                                                                const bf16* __restrict__ dout, long lddo,
                                                                const float* __restrict__ lse,
                                                                bf16* __restrict__ dqkv, long lddq, int N, int H,
                                                                int dh, float scale, float sl2, uint32_t thr,
                                                                float dscale, uint64_t seed, float* __restrict__ cs_part) {
+  constexpr int NB = 8;
   seed = step_seed(seed);
   constexpr int IMG = NB * 32 * 128;
   __shared__ __attribute__((aligned(1024))) char lds[fused_lds_bytes<NB>()];
@@ -1942,18 +1944,6 @@ __global__ void attn_f32_grads(const float* P, const float* G, const float* qkv,
   o[2 * D] = dv;
 }
 
-#define FER_NB_SWITCH(NB, ...)     \
-  switch (NB) {                    \
-    case 1: { constexpr int NB_ = 1; __VA_ARGS__; } break; \
-    case 2: { constexpr int NB_ = 2; __VA_ARGS__; } break; \
-    case 3: { constexpr int NB_ = 3; __VA_ARGS__; } break; \
-    case 4: { constexpr int NB_ = 4; __VA_ARGS__; } break; \
-    case 5: { constexpr int NB_ = 5; __VA_ARGS__; } break; \
-    case 6: { constexpr int NB_ = 6; __VA_ARGS__; } break; \
-    case 7: { constexpr int NB_ = 7; __VA_ARGS__; } break; \
-    default: { constexpr int NB_ = 8; __VA_ARGS__; } break; \
-  }
-
 }  // namespace fer
 
 using namespace fer;
@@ -1987,15 +1977,6 @@ static int g_fwd_kernel = 0;
 static int64_t lse_floats(int B, int N, int H) { return ((int64_t)B * H * N + 63) / 64 * 64; }
 // persistent kernels walk a fixed blockIdx stride instead of the work queue (fer_set_persistent_mode)
 static bool fixed_stride() { return fixed_stride_mode(); }
-static int n_cus() {
-  static const int n = [] {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      c = 256;
-    return c > 0 ? c : 256;
-  }();
-  return n;
-}
 
 // Workgroups per CU a persistent attention kernel can hold (registers / LDS; the occupancy API,
 // queried once per instantiation): the small-N instantiations (w+ latents: N = 19, one key block)
@@ -2040,10 +2021,8 @@ extern "C" int fer_attention_fwd(int dtype, const void* qkv, int64_t ld_qkv, voi
     return set_error("attention_fwd(bf16): qkv or out exceeds 2 GiB");
   const float sl2 = scale * LOG2E;
   if (N <= 256 && dh <= 64 && N > 224) {  // NB = 8: 9 waves would not fit 2/SIMD
-    const int nb = (N + 31) / 32;
-    FER_NB_SWITCH(nb, hipLaunchKernelGGL(attn_fwd_bf16<NB_>, dim3(B * H), dim3(64 * NB_), 0, st, (const bf16*)qkv,
-                                         (long)ld_qkv, (bf16*)out, (long)ld_out, lse, N, H, dh, sl2, drop_thresh,
-                                         drop_scale, seed));
+    hipLaunchKernelGGL(attn_fwd_bf16, dim3(B * H), dim3(512), 0, st, (const bf16*)qkv, (long)ld_qkv, (bf16*)out,
+                       (long)ld_out, lse, N, H, dh, sl2, drop_thresh, drop_scale, seed);
   } else if (N <= 224 && dh <= 64 && (g_fwd_kernel == 2 || (g_fwd_kernel == 0 && drop_thresh && (N + 31) / 32 >= 4))) {
     const int nb = (N + 31) / 32;
     uint32_t* mask = (drop_thresh && pers_path(dtype, N, dh)) ? (uint32_t*)(lse + lse_floats(B, N, H)) : nullptr;
@@ -2068,7 +2047,7 @@ extern "C" int fer_attention_fwd(int dtype, const void* qkv, int64_t ld_qkv, voi
   } break;
     switch (nb) { FER_FOCC(1) FER_FOCC(2) FER_FOCC(3) FER_FOCC(4) FER_FOCC(5) FER_FOCC(6) FER_FOCC(7) }
 #undef FER_FOCC
-    const int grid = std::min(B * H, n_cus() * occ);
+    const int grid = std::min(B * H, num_cus() * occ);
     const WqArgs wq = fixed_stride() ? WqArgs{} : wq_prepare_here(st, grid, B * H);
 #define FER_FPERS(NBV)                                                                                     \
   case NBV:                                                                                                \
@@ -2147,7 +2126,7 @@ extern "C" int fer_attention_bwd(int dtype, const void* qkv, int64_t ld_qkv, con
   } break;
     switch (nb) { FER_BOCC(1) FER_BOCC(2) FER_BOCC(3) FER_BOCC(4) FER_BOCC(5) FER_BOCC(6) FER_BOCC(7) }
 #undef FER_BOCC
-    const int grid = std::min(B * H, n_cus() * occ);
+    const int grid = std::min(B * H, num_cus() * occ);
     const WqArgs wq = fixed_stride() ? WqArgs{} : wq_prepare_here(st, grid, B * H);
 #define FER_PERS(NBV)                                                                                          \
   case NBV:                                                                                                    \
@@ -2168,18 +2147,10 @@ extern "C" int fer_attention_bwd(int dtype, const void* qkv, int64_t ld_qkv, con
   }
   if (nb <= 8 && dh <= 64) {
     if (colsum) ws = reduction_ws(ws, (size_t)B * D3 * 4, D3, st);
-#define FER_FUSED(NBV)                                                                                       \
-  case NBV:                                                                                                  \
-    hipLaunchKernelGGL(attn_bwd_fused_bf16<NBV>, dim3(B * H), dim3(64 * NBV), 0, st, (const bf16*)qkv,       \
-                       (long)ld_qkv, (const bf16*)out, (long)ld_out, (const bf16*)dout, (long)ld_dout, lse,   \
-                       (bf16*)dqkv, (long)ld_dqkv, N, H, dh, scale, sl2, drop_thresh, drop_scale, seed,      \
-                       colsum ? ws : nullptr);                                                              \
-    break;
-    switch (nb) {  // every N <= 256
-      FER_FUSED(1) FER_FUSED(2) FER_FUSED(3) FER_FUSED(4) FER_FUSED(5) FER_FUSED(6) FER_FUSED(7)
-      FER_FUSED(8)
-    }
-#undef FER_FUSED
+    // 224 < N <= 256 (N <= 224 took the persistent path above): eight query blocks
+    hipLaunchKernelGGL(attn_bwd_fused_bf16, dim3(B * H), dim3(512), 0, st, (const bf16*)qkv, (long)ld_qkv,
+                       (const bf16*)out, (long)ld_out, (const bf16*)dout, (long)ld_dout, lse, (bf16*)dqkv,
+                       (long)ld_dqkv, N, H, dh, scale, sl2, drop_thresh, drop_scale, seed, colsum ? ws : nullptr);
     int rc = hip_check("attention_bwd_bf16_fused");
     if (rc || !colsum) return rc;
     part_reduce(ws, B, D3, D3, D3, colsum, nullptr, nullptr, colsum_accumulate, nullptr, st);

@@ -32,6 +32,16 @@ static int g_fixed_stride = [] {  // fer_set_persistent_mode; FERVIT_FIXED_STRID
 
 bool fixed_stride_mode() { return g_fixed_stride == 1; }
 
+int num_cus() {
+  static const int n = [] {
+    int dev = 0, c = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      c = 256;
+    return c > 0 ? c : 256;
+  }();
+  return n;
+}
+
 }  // namespace fer
 
 extern "C" int fer_set_persistent_mode(int mode) {

@@ -34,6 +34,8 @@ int hip_check(const char* what);
 // persistent GEMM / attention kernels: walk a fixed blockIdx stride instead of the work queue
 // (fer_set_persistent_mode(1))
 bool fixed_stride_mode();
+// compute units of the current device (256 when the query fails), asked once per process
+int num_cus();
 int gemm_launch(const GemmDesc& d, const EpiArgs& e, hipStream_t st);
 inline int ceil_div(long a, long b);
 // out_k[c % seg] (+)= scale * sum_b part[b*ld + c]  (deterministic, misc.hip)

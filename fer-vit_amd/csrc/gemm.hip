@@ -411,9 +411,10 @@ FER_DEV void split_tile_of(int tiles_m, int tiles_n, int& tm, int& tn, int& ks) 
 
 // ------------------------------------------------------------- LDS-DMA stage
 constexpr int BK = 64;
+constexpr int MT = 16;  // MFMA block edge: v_mfma_f32_16x16x32_bf16 is the only form
 // KC image [rows][BKT k] (2*BKT-byte rows). BKT=64: chunk ^= (row>>1)&7. BKT=32 (4 rows per
 // 256 B): chunk ^= s(row>>2) with s = 0,0,2,2,1,1,3,3 — conflict-free for the ds_read_b128
-// lane groups of both the 32x32 (16 rows, one chunk) and 16x16 (rows x 2 chunks) reads.
+// lane groups of the 16x16 fragment reads (rows x 2 chunks).
 template <int BKT> FER_DEV int kc_swz(int row) {
   if constexpr (BKT == 64) return (row >> 1) & 7;
   else return (((row >> 3) & 1) << 1) | ((row >> 4) & 1);
@@ -424,12 +425,9 @@ template <int BKT> FER_DEV int kc_swz(int row) {
 // (one add per piece per K-step). For KC the K-step adds k0*2 bytes, for MN the wave-uniform
 // k0*ld*2. `kof` (the lane's K inside the stage) is checked only on a partial last K-step.
 // MN tr-read image swizzle (16-byte chunk XOR by K row), see read_frag.
-template <int MT> FER_DEV int mn_swz_t(int k) {
-  if constexpr (MT == 32) return (k & 3) << 2;               // 4 rows x 64 B per 32-lane half
-  else return ((k & 3) | (((k >> 3) & 1) << 2)) << 1;       // 8 rows x 32 B per 32-lane half
-}
+FER_DEV int mn_swz(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 1; }  // 8 rows x 32 B per 32-lane half
 
-template <int R, bool KC, int NW, int MT, int BKT = BK>
+template <int R, bool KC, int NW, int BKT = BK>
 struct DmaPlan {
   static constexpr int NI = R * BKT * 2 / 1024 / NW;
   static_assert(NI * NW * 1024 == R * BKT * 2, "tile/wave mismatch");
@@ -453,7 +451,7 @@ struct DmaPlan {
         constexpr int RB = R * 2;
         const int byte = gi * 1024 + lane * 16;
         const int k = byte / RB;
-        const int c = ((byte % RB) >> 4) ^ mn_swz_t<MT>(k);
+        const int c = ((byte % RB) >> 4) ^ mn_swz(k);
         const int gc = r0 + c * 8;
         ok = gc < rmax;
         kof[i] = k;
@@ -479,46 +477,30 @@ struct DmaPlan {
   }
 };
 
-// MFMA operand fragments. MT = 32: v_mfma_f32_32x32x16_bf16, lane l holds index i0 + (l&31),
-// k = 16kk + 8(l>>5) + j. MT = 16: v_mfma_f32_16x16x32_bf16, lane l holds index i0 + (l&15),
+// MFMA operand fragments for v_mfma_f32_16x16x32_bf16: lane l holds index i0 + (l&15),
 // k = 32kk + 8(l>>4) + j (j = 0..7). KC images are read with ds_read_b128, MN images with two
 // ds_read_b64_tr_b16 (rows k..k+3 and k+4..k+7 of 16 consecutive indices).
 
-template <int MT, int R, bool KC, int BKT = BK>
+template <int R, bool KC, int BKT = BK>
 FER_DEV bf16x8 read_frag(const char* lds_tile, int i0, int kk, int lane) {
   if constexpr (KC) {
-    const int row = i0 + (MT == 32 ? (lane & 31) : (lane & 15));
-    const int ch = MT == 32 ? 2 * kk + (lane >> 5) : 4 * kk + (lane >> 4);
+    const int row = i0 + (lane & 15);
+    const int ch = 4 * kk + (lane >> 4);
     return *(const bf16x8*)(lds_tile + row * (BKT * 2) + ((ch ^ kc_swz<BKT>(row)) << 4));
   } else {
     constexpr int RB = R * 2;
     const int gg = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    int k1, c;
-    if constexpr (MT == 32) {
-      k1 = 16 * kk + 8 * (gg >> 1) + q;
-      c = ((i0 + 16 * (gg & 1)) >> 3) + (p >> 1);
-    } else {
-      k1 = 32 * kk + 8 * gg + q;
-      c = (i0 >> 3) + (p >> 1);
-    }
-    const int k2 = k1 + 4;
-    const char* a1 = lds_tile + k1 * RB + ((c ^ mn_swz_t<MT>(k1)) << 4) + (p & 1) * 8;
-    const char* a2 = lds_tile + k2 * RB + ((c ^ mn_swz_t<MT>(k2)) << 4) + (p & 1) * 8;
+    const int k1 = 32 * kk + 8 * gg + q, k2 = k1 + 4;
+    const int c = (i0 >> 3) + (p >> 1);
+    const char* a1 = lds_tile + k1 * RB + ((c ^ mn_swz(k1)) << 4) + (p & 1) * 8;
+    const char* a2 = lds_tile + k2 * RB + ((c ^ mn_swz(k2)) << 4) + (p & 1) * 8;
     short4_t t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)a1);
     short4_t t2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)a2);
     return cat8(t1, t2);
   }
 }
 
-template <int MT> struct Acc;
-template <> struct Acc<32> { typedef f32x16 T; };
-template <> struct Acc<16> { typedef f32x4 T; };
-
-template <int MT>
-FER_DEV typename Acc<MT>::T mfma(bf16x8 a, bf16x8 b, typename Acc<MT>::T c) {
-  if constexpr (MT == 32) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
+FER_DEV f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 #ifdef FER_GEMM_STAMPS
 // diagnostic build only: s_memtime at the epilogue's stage boundaries (lane 0 of waves 0 and 4 of
@@ -542,12 +524,13 @@ __device__ unsigned long long g_epst[2][16];
 // workgroup) is bar_lds (lgkmcnt(0) + s_barrier): the barriers order LDS staging only. (With no
 // LDS-DMA in flight hipcc lowers __syncthreads to the same two instructions; bar_lds makes sure no
 // vmcnt(0) -- a wait for every earlier output store -- can appear there.)
-// Accumulator element (i, j, q, r) -> tile row/col. Split-K partials go to
+// Accumulator block (i, j), element r -> tile row 16j + (lane & 15), column 16i + 4(lane >> 4) + r
+// of the wave's region. Split-K partials go to
 // the fp32 slab; otherwise each wave-row half of the tile (in EPC row chunks) is staged
 // through LDS as fp32 with padded rows and every thread applies the epilogue on 4 consecutive
 // columns of one row: all global traffic of the epilogue is row-contiguous.
-template <int BM, int BN, int WM, int WN, int MT, int EPC, int SMEMB, int EK = EPI_GEN, typename AccT, int FN, int FM>
-FER_DEV void tile_epilogue(const GemmArgs& g, const EpiArgs& e, AccT (&acc)[FN][FM], char* smem, int m0, int n0,
+template <int BM, int BN, int WM, int WN, int EPC, int SMEMB, int EK = EPI_GEN, int FN, int FM>
+FER_DEV void tile_epilogue(const GemmArgs& g, const EpiArgs& e, f32x4 (&acc)[FN][FM], char* smem, int m0, int n0,
                            int ks, int wm, int wn, int lane, uint64_t seed) {
   int tid_ = threadIdx.x;  // laundered: not hoisted out of a persistent tile loop
   asm volatile("" : "+v"(tid_));
@@ -556,9 +539,10 @@ FER_DEV void tile_epilogue(const GemmArgs& g, const EpiArgs& e, AccT (&acc)[FN][
 #endif
   EP_STAMP(0);
   constexpr int TM = BM / WM, TN = BN / WN;
-  constexpr int NQ = MT == 32 ? 4 : 1;
-  const int lr = MT == 32 ? (lane & 31) : (lane & 15);
-  const int lc = MT == 32 ? 4 * (lane >> 5) : 4 * (lane >> 4);
+  // f32x4 pieces per accumulator block. The one-trip q loops below stay as written: folded by hand,
+  // the compiler reassociates the row / column arithmetic of every kernel that uses this epilogue.
+  constexpr int NQ = 1;
+  const int lr = lane & 15, lc = 4 * (lane >> 4);
   if (g.partial) {  // split-K partial slab, fp32 [split][M][N] (reduced by splitk_reduce_kernel)
     float* ws = g.ws + (long)ks * g.M * g.N;
 #pragma unroll
@@ -847,19 +831,17 @@ FER_DEV void tile_epilogue(const GemmArgs& g, const EpiArgs& e, AccT (&acc)[FN][
   }
 }
 
-// Wave grid WM x WN over a BM x BN tile; each wave owns (BM/WM) x (BN/WN) as MT x MT MFMA
+// Wave grid WM x WN over a BM x BN tile; each wave owns (BM/WM) x (BN/WN) as 16 x 16 MFMA
 // blocks. The MFMA is issued with the B fragment as the instruction's A operand, so the
-// accumulator's column index is m: for MT=32, lane l holds m = l&31 and n = 8q + 4(l>>5) + r
-// (q, r = 0..3); for MT=16, m = l&15 and n = 4(l>>4) + r.
-// Double-buffered BK=64 stages. Per K-step t: all LDS-DMA pieces of stage t+1, then SS
-// substeps of  ds_read(t, kk+1) | MFMAs(t, kk); then vmcnt(0) + s_barrier hands t+1 over.
-template <int BM, int BN, int WM, int WN, bool AKC, bool BKC, int MT, int EK = EPI_GEN>
+// accumulator's column index is m: lane l holds m = l&15 and n = 4(l>>4) + r (r = 0..3).
+// Double-buffered BK=64 stages. Per K-step t: all LDS-DMA pieces of stage t+1, then SS = 2
+// substeps (K = 32 each) of  ds_read(t, kk+1) | MFMAs(t, kk); then vmcnt(0) + s_barrier hands t+1 over.
+template <int BM, int BN, int WM, int WN, bool AKC, bool BKC, int EK = EPI_GEN>
 __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g, EpiArgs e) {
-  typedef typename Acc<MT>::T AccT;
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN;
   constexpr int FM = TM / MT, FN = TN / MT;
-  constexpr int SS = MT == 32 ? 4 : 2;
+  constexpr int SS = BK / 32;  // MFMA K-steps per stage
   constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
   constexpr int STAGE = A_BYTES + B_BYTES;
   constexpr int EROWS = BM / 2, ELD = BN + 4;                         // epilogue staging: half tile fp32
@@ -884,17 +866,17 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g, 
 
   const u32x4 ra = rsrc4(g.A);
   const u32x4 rb = rsrc4(g.B);
-  DmaPlan<BM, AKC, NW, MT> pa;
-  DmaPlan<BN, BKC, NW, MT> pb;
+  DmaPlan<BM, AKC, NW> pa;
+  DmaPlan<BN, BKC, NW> pb;
   pa.init(wave, lane, g.lda, m0, g.M);
   pb.init(wave, lane, g.ldb, n0, g.N);
   const int ktail = kbeg + (nk - 1) * BK;  // first K of the last step (only step that can be partial)
 
-  AccT acc[FN][FM];
+  f32x4 acc[FN][FM];
 #pragma unroll
   for (int i = 0; i < FN; ++i)
 #pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = AccT{};
+    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{};
 
   bf16x8 af[FM], bfr[FN];
   if (nk > 0) {
@@ -904,9 +886,9 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g, 
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 #pragma unroll
-    for (int i = 0; i < FN; ++i) bfr[i] = read_frag<MT, BN, BKC>(smem + A_BYTES, wn * TN + i * MT, 0, lane);
+    for (int i = 0; i < FN; ++i) bfr[i] = read_frag<BN, BKC>(smem + A_BYTES, wn * TN + i * MT, 0, lane);
 #pragma unroll
-    for (int j = 0; j < FM; ++j) af[j] = read_frag<MT, BM, AKC>(smem, wm * TM + j * MT, 0, lane);
+    for (int j = 0; j < FM; ++j) af[j] = read_frag<BM, AKC>(smem, wm * TM + j * MT, 0, lane);
   }
   for (int t = 0; t < nk; ++t) {
     const char* cur = smem + (t & 1) * STAGE;
@@ -923,14 +905,14 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g, 
       bf16x8 an[FM], bn[FN];
       if (kk < SS - 1) {
 #pragma unroll
-        for (int i = 0; i < FN; ++i) bn[i] = read_frag<MT, BN, BKC>(cur + A_BYTES, wn * TN + i * MT, kk + 1, lane);
+        for (int i = 0; i < FN; ++i) bn[i] = read_frag<BN, BKC>(cur + A_BYTES, wn * TN + i * MT, kk + 1, lane);
 #pragma unroll
-        for (int j = 0; j < FM; ++j) an[j] = read_frag<MT, BM, AKC>(cur, wm * TM + j * MT, kk + 1, lane);
+        for (int j = 0; j < FM; ++j) an[j] = read_frag<BM, AKC>(cur, wm * TM + j * MT, kk + 1, lane);
       }
 #pragma unroll
       for (int j = 0; j < FM; ++j)
 #pragma unroll
-        for (int i = 0; i < FN; ++i) acc[i][j] = mfma<MT>(bfr[i], af[j], acc[i][j]);
+        for (int i = 0; i < FN; ++i) acc[i][j] = mfma(bfr[i], af[j], acc[i][j]);
       if (kk < SS - 1) {
 #pragma unroll
         for (int i = 0; i < FN; ++i) bfr[i] = bn[i];
@@ -943,30 +925,28 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g, 
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
 #pragma unroll
-      for (int i = 0; i < FN; ++i) bfr[i] = read_frag<MT, BN, BKC>(nxt + A_BYTES, wn * TN + i * MT, 0, lane);
+      for (int i = 0; i < FN; ++i) bfr[i] = read_frag<BN, BKC>(nxt + A_BYTES, wn * TN + i * MT, 0, lane);
 #pragma unroll
-      for (int j = 0; j < FM; ++j) af[j] = read_frag<MT, BM, AKC>(nxt, wm * TM + j * MT, 0, lane);
+      for (int j = 0; j < FM; ++j) af[j] = read_frag<BM, AKC>(nxt, wm * TM + j * MT, 0, lane);
     }
   }
 
-  tile_epilogue<BM, BN, WM, WN, MT, (BM >= 256 ? 2 : 1), SMEM, EK>(g, e, acc, smem, m0, n0, ks, wm, wn, lane,
-                                                                     e.drop_thresh ? step_seed(e.seed) : 0);
+  tile_epilogue<BM, BN, WM, WN, (BM >= 256 ? 2 : 1), SMEM, EK>(g, e, acc, smem, m0, n0, ks, wm, wn, lane,
+                                                                 e.drop_thresh ? step_seed(e.seed) : 0);
 }
 
-// Ring variant: BK=32 stages in an NST-slot LDS ring, LDS-DMA issued NST-1 K-steps ahead and
-// spread over the substeps (so no wave blocks on a burst of DMA issue and each stage has
-// ~NST-2 K-steps to land). Per K-step t, in its last substep: counted vmcnt for stage t+1,
-// s_barrier, fragment reads of (t+1, 0) — behind the MFMAs of (t, last). The slot refilled in
+// Ring variant: BK=32 stages (one MFMA K-step each) in a 4-slot LDS ring, LDS-DMA issued 3 K-steps
+// ahead (each stage has ~2 K-steps to land). Per K-step t: counted vmcnt for stage t+1,
+// s_barrier, fragment reads of stage t+1 — behind the MFMAs of stage t. The slot refilled in
 // step t is the one read in step t-1, released by the barrier of step t-1... which every wave
 // passed after issuing (and before consuming) those reads.
-template <int BM, int BN, int WM, int WN, bool AKC, bool BKC, int MT, int NST>
+template <int BM, int BN, int WM, int WN, bool AKC, bool BKC>
 __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(GemmArgs g, EpiArgs e) {
-  typedef typename Acc<MT>::T AccT;
   constexpr int RBK = 32;
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN;
   constexpr int FM = TM / MT, FN = TN / MT;
-  constexpr int SS = MT == 32 ? 2 : 1;
+  constexpr int NST = 4;       // ring slots (the vmcnt bookkeeping below is written for 4)
   constexpr int PD = NST - 1;  // prefetch distance in K-steps
   constexpr int A_BYTES = BM * RBK * 2, B_BYTES = BN * RBK * 2;
   constexpr int STAGE = A_BYTES + B_BYTES;
@@ -991,21 +971,20 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(GemmArgs g, 
 
   const u32x4 ra = rsrc4(g.A);
   const u32x4 rb = rsrc4(g.B);
-  typedef DmaPlan<BM, AKC, NW, MT, RBK> PA;
-  typedef DmaPlan<BN, BKC, NW, MT, RBK> PB;
+  typedef DmaPlan<BM, AKC, NW, RBK> PA;
+  typedef DmaPlan<BN, BKC, NW, RBK> PB;
   PA pa;
   PB pb;
   pa.init(wave, lane, g.lda, m0, g.M);
   pb.init(wave, lane, g.ldb, n0, g.N);
   const int ktail = kbeg + (nk - 1) * RBK;
-  constexpr int PER = PA::NI + PB::NI;      // DMA instructions per stage per wave
-  constexpr int EARLY = SS > 1 ? PA::NI : 0;  // of those, issued before the last substep
+  constexpr int PER = PA::NI + PB::NI;  // DMA instructions per stage per wave
 
-  AccT acc[FN][FM];
+  f32x4 acc[FN][FM];
 #pragma unroll
   for (int i = 0; i < FN; ++i)
 #pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = AccT{};
+    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{};
 
   auto slot = [&](int st) -> char* { return smem + (st % NST) * STAGE; };
   auto issue_a = [&](int st) {
@@ -1032,159 +1011,46 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_ring_kernel(GemmArgs g, 
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 #pragma unroll
-    for (int i = 0; i < FN; ++i) bfr[i] = read_frag<MT, BN, BKC, RBK>(smem + A_BYTES, wn * TN + i * MT, 0, lane);
+    for (int i = 0; i < FN; ++i) bfr[i] = read_frag<BN, BKC, RBK>(smem + A_BYTES, wn * TN + i * MT, 0, lane);
 #pragma unroll
-    for (int j = 0; j < FM; ++j) af[j] = read_frag<MT, BM, AKC, RBK>(smem, wm * TM + j * MT, 0, lane);
+    for (int j = 0; j < FM; ++j) af[j] = read_frag<BM, AKC, RBK>(smem, wm * TM + j * MT, 0, lane);
   }
-  static_assert(NST == 4, "vmcnt bookkeeping below assumes a 4-slot ring (PD = 3)");
-  // One MFMA substep (t, kk) on fragments (ca, cb), the next substep's fragments read into (na, nb).
-  // The two fragment sets alternate by substep (SS = 2: within a K-step; SS = 1: the K loop unrolled by
-  // two): with one set copied forward at every substep's end, those copies were 48 v_mov per K-step
-  // (the loads into the next set are in flight while the MFMAs read the current one).
+  // One K-step t on fragments (ca, cb), the next K-step's fragments read into (na, nb). The two
+  // fragment sets alternate by K-step (the K loop is unrolled by two): with one set copied forward at
+  // every step's end, those copies were 48 v_mov per K-step (the loads into the next set are in flight
+  // while the MFMAs read the current one).
   bf16x8 af1[FM], bf1[FN];
-  auto sub = [&](int t, int kk, const bf16x8 (&ca)[FM], const bf16x8 (&cb)[FN], bf16x8 (&na)[FM], bf16x8 (&nb)[FN]) {
-    const char* cur = slot(t);
+  auto step = [&](int t, const bf16x8 (&ca)[FM], const bf16x8 (&cb)[FN], bf16x8 (&na)[FM], bf16x8 (&nb)[FN]) {
     const bool pf = t + PD < nk;
-    if (kk < SS - 1) {
+    if (t + 1 < nk) {
+      // stage t+1 landed; stage t+2 may be in flight (pf implies t + 2 < nk: the first test is
+      // redundant, but without it the compiler emits the K loop differently)
+      if (pf) wait_vm<PER>();
+      else if (t + 2 < nk) wait_vm<PER>();
+      else wait_vm<0>();
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      const char* nx = slot(t + 1);
 #pragma unroll
-      for (int i = 0; i < FN; ++i) nb[i] = read_frag<MT, BN, BKC, RBK>(cur + A_BYTES, wn * TN + i * MT, kk + 1, lane);
+      for (int i = 0; i < FN; ++i) nb[i] = read_frag<BN, BKC, RBK>(nx + A_BYTES, wn * TN + i * MT, 0, lane);
 #pragma unroll
-      for (int j = 0; j < FM; ++j) na[j] = read_frag<MT, BM, AKC, RBK>(cur, wm * TM + j * MT, kk + 1, lane);
-      if (pf) issue_a(t + PD);
-    } else {
-      if (t + 1 < nk) {
-        // stage t+1 landed; stage t+2 and (SS>1) the A pieces of stage t+3 may be in flight
-        if (pf) wait_vm<PER + EARLY>();
-        else if (t + 2 < nk) wait_vm<PER>();
-        else wait_vm<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const char* nx = slot(t + 1);
-#pragma unroll
-        for (int i = 0; i < FN; ++i) nb[i] = read_frag<MT, BN, BKC, RBK>(nx + A_BYTES, wn * TN + i * MT, 0, lane);
-#pragma unroll
-        for (int j = 0; j < FM; ++j) na[j] = read_frag<MT, BM, AKC, RBK>(nx, wm * TM + j * MT, 0, lane);
-      }
-      if (pf) {
-        if (SS == 1) issue_a(t + PD);
-        issue_b(t + PD);
-      }
+      for (int j = 0; j < FM; ++j) na[j] = read_frag<BM, AKC, RBK>(nx, wm * TM + j * MT, 0, lane);
+    }
+    if (pf) {
+      issue_a(t + PD);
+      issue_b(t + PD);
     }
 #pragma unroll
     for (int j = 0; j < FM; ++j)
 #pragma unroll
-      for (int i = 0; i < FN; ++i) acc[i][j] = mfma<MT>(cb[i], ca[j], acc[i][j]);
+      for (int i = 0; i < FN; ++i) acc[i][j] = mfma(cb[i], ca[j], acc[i][j]);
   };
-  if constexpr (SS == 2) {
-    for (int t = 0; t < nk; ++t) {
-      sub(t, 0, af, bfr, af1, bf1);
-      sub(t, 1, af1, bf1, af, bfr);
-    }
-  } else {
-    for (int t = 0; t < nk; t += 2) {
-      sub(t, 0, af, bfr, af1, bf1);
-      if (t + 1 < nk) sub(t + 1, 0, af1, bf1, af, bfr);
-    }
+  for (int t = 0; t < nk; t += 2) {
+    step(t, af, bfr, af1, bf1);
+    if (t + 1 < nk) step(t + 1, af1, bf1, af, bfr);
   }
-  tile_epilogue<BM, BN, WM, WN, MT, EPC, NST * STAGE>(g, e, acc, smem, m0, n0, ks, wm, wn, lane,
+  tile_epilogue<BM, BN, WM, WN, EPC, NST * STAGE>(g, e, acc, smem, m0, n0, ks, wm, wn, lane,
                                                       e.drop_thresh ? step_seed(e.seed) : 0);
-}
-
-// ===================================================================== ping-pong kernel
-// 256x128 tile on 4 waves (2 x 2, each a 128x64 accumulator tile of 16x16 blocks), BK=32 stages in
-// a 3-slot LDS ring (72 KB): small enough for TWO workgroups per CU, so one workgroup's epilogue
-// (VALU: bias, GELU, dropout hashing; LDS staging; stores) runs beside the other's MFMA main loop
-// instead of idling the matrix pipe. One barrier per K-step: it publishes stage t (every wave
-// waited for its own DMA pieces of it) and releases slot (t-1)%3, which is refilled with stage
-// t+2 right after it (two K-steps of DMA slack). Fragments of a K-step are read after the
-// barrier; the partner workgroup's waves fill the SIMD while they land.
-template <bool AKC, bool BKC, int EK = EPI_GEN>
-__global__ __launch_bounds__(256, 2) void gemm_pp_kernel(GemmArgs g, EpiArgs e) {
-  typedef f32x4 AccT;
-  constexpr int BM = 256, BN = 128, WM = 2, WN = 2, MT = 16, RBK = 32, NST = 3, NW = 4;
-  constexpr int TM = BM / WM, TN = BN / WN, FM = TM / MT, FN = TN / MT;
-  constexpr int A_BYTES = BM * RBK * 2, B_BYTES = BN * RBK * 2, STAGE = A_BYTES + B_BYTES;
-  __shared__ __attribute__((aligned(1024))) char smem[NST * STAGE];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave % WM, wn = wave / WM;
-  int tm, tn, ks = 0;
-  if (gridDim.y > 1) split_tile_of(g.tiles_m, g.tiles_n, tm, tn, ks);
-  else {
-    tile_of(blockIdx.x, g.tiles_m, g.tiles_n, tm, tn);
-    ks = blockIdx.y;
-  }
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int kbeg = ks * g.k_chunk;
-  const int kend = min(g.K, kbeg + g.k_chunk);
-  const int nk = (kend - kbeg + RBK - 1) / RBK;
-  const int ktail = kbeg + (nk - 1) * RBK;
-  const u32x4 ra = rsrc4(g.A);
-  const u32x4 rb = rsrc4(g.B);
-  typedef DmaPlan<BM, AKC, NW, MT, RBK> PA;
-  typedef DmaPlan<BN, BKC, NW, MT, RBK> PB;
-  PA pa;
-  PB pb;
-  pa.init(wave, lane, g.lda, m0, g.M);
-  pb.init(wave, lane, g.ldb, n0, g.N);
-  constexpr int PER = PA::NI + PB::NI;  // DMA instructions per stage per wave
-  auto slot = [&](int st) -> char* { return smem + (st % NST) * STAGE; };
-  auto issue = [&](int st) {
-    const int k0 = kbeg + st * RBK;
-    pa.issue(ra, slot(st), wave, g.lda, k0, kend, k0 == ktail);
-    pb.issue(rb, slot(st) + A_BYTES, wave, g.ldb, k0, kend, k0 == ktail);
-  };
-  AccT acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = AccT{};
-  if (nk > 0) issue(0);
-  if (nk > 1) issue(1);
-  for (int t = 0; t < nk; ++t) {
-    if (t + 1 < nk) wait_vm<PER>();  // stage t landed (own pieces); stage t+1 may fly
-    else wait_vm<0>();
-    __builtin_amdgcn_s_barrier();   // stage t published; slot (t-1)%3 free
-    asm volatile("" ::: "memory");
-    if (t + 2 < nk) issue(t + 2);
-    const char* cur = slot(t);
-    bf16x8 af[FM], bfr[FN];
-#pragma unroll
-    for (int i = 0; i < FN; ++i) bfr[i] = read_frag<MT, BN, BKC, RBK>(cur + A_BYTES, wn * TN + i * MT, 0, lane);
-#pragma unroll
-    for (int j = 0; j < FM; ++j) af[j] = read_frag<MT, BM, AKC, RBK>(cur, wm * TM + j * MT, 0, lane);
-#pragma unroll
-    for (int j = 0; j < FM; ++j)
-#pragma unroll
-      for (int i = 0; i < FN; ++i) acc[i][j] = mfma<MT>(bfr[i], af[j], acc[i][j]);
-  }
-  bar_lds();  // every wave's fragment reads are done: the ring becomes epilogue staging
-  tile_epilogue<BM, BN, WM, WN, MT, 2, NST * STAGE, EK>(g, e, acc, smem, m0, n0, ks, wm, wn, lane,
-                                                         e.drop_thresh ? step_seed(e.seed) : 0);
-}
-
-template <bool AKC, bool BKC>
-static int launch_pp(GemmArgs g, const EpiArgs& e, hipStream_t st) {
-  g.tiles_m = (g.M + 255) / 256;
-  g.tiles_n = (g.N + 127) / 128;
-  const dim3 grid(g.tiles_m * g.tiles_n, g.splits);
-  // fixed-flag epilogue kinds as in the 8-phase kernel (K-contiguous operands, no split-K)
-  const int ek = (AKC && BKC && !g.partial) ? epi_kind(e, g.M, g.N) : EPI_GEN;
-#define FER_PPK(K) hipLaunchKernelGGL((gemm_pp_kernel<AKC, BKC, K>), grid, dim3(256), 0, st, g, e)
-  if constexpr (AKC && BKC) {
-    switch (ek) {
-      case EPI_STORE: FER_PPK(EPI_STORE); break;
-      case EPI_GATE: FER_PPK(EPI_GATE); break;
-      case EPI_GATER: FER_PPK(EPI_GATER); break;
-      case EPI_RES2: FER_PPK(EPI_RES2); break;
-      case EPI_MUL2: FER_PPK(EPI_MUL2); break;
-      default: FER_PPK(EPI_GEN); break;
-    }
-  } else {
-    FER_PPK(EPI_GEN);
-  }
-#undef FER_PPK
-  return 0;
 }
 
 // ===================================================================== 8-phase kernel
@@ -1204,7 +1070,7 @@ static int launch_pp(GemmArgs g, const EpiArgs& e, hipStream_t st) {
 // (each >= 3 phases after its last read in the same buffer). Waits: q=3 retires A0/B0(T+1)
 // (vmcnt 6: A1, B1(T+1), A0(T+2) may fly), q=0 retires A1/B1(T) (vmcnt 4); a unit is read one
 // phase after the wait that retires it (the barrier between publishes other waves' DMA).
-template <bool KC, int MT, bool ISA>
+template <bool KC, bool ISA>
 struct UnitPlan {
   uint32_t base[2];
   int kof[2];
@@ -1228,7 +1094,7 @@ struct UnitPlan {
       } else {
         const int byte = gi * 1024 + lane * 16;
         const int k = byte >> 8;
-        const int c = ((byte & 255) >> 4) ^ mn_swz_t<MT>(k);
+        const int c = ((byte & 255) >> 4) ^ mn_swz(k);
         const int gc = r0 + map(c * 8, q);
         ok = gc < rmax;
         kof[i] = k;
@@ -1382,13 +1248,12 @@ FER_DEV void tile_epilogue_wp(const GemmArgs& g, const EpiArgs& e, f32x4 (&acc)[
 // claim_slot (work-queue mode): thread 0 claims a tile at the start of this one, before the
 // prologue's operand DMA, and parks the id in that LDS word after the prologue's wait (which
 // retires the atomic together with the previous tile's epilogue stores and the first K-tile)
-template <bool AKC, bool BKC, int MT, int EK>
+template <bool AKC, bool BKC, int EK>
 FER_DEV void tile_8ph(const GemmArgs& g, const EpiArgs& e, int bid, char* smem, lds_vint* claim_slot, uint64_t seed) {
-  typedef typename Acc<MT>::T AccT;
   constexpr int UNIT = 16384, BUF = 4 * UNIT;  // A0 A1 B0 B1
   constexpr int FM = 128 / MT, FN = 64 / MT;   // MFMA blocks per wave (rows, cols)
   constexpr int QJ = FM / 2, QI = FN / 2;      // per quadrant
-  constexpr int KS = 64 / (MT == 32 ? 16 : 32);  // MFMA K-steps per K-tile
+  constexpr int KS = 64 / 32;                  // MFMA K-steps per K-tile
   // launder the thread index: lane-derived addressing is recomputed per tile instead of being
   // hoisted out of the persistent loop (hoisting pushed the kernel past 256 VGPRs)
   int tid = threadIdx.x;
@@ -1416,8 +1281,8 @@ FER_DEV void tile_8ph(const GemmArgs& g, const EpiArgs& e, int bid, char* smem, 
 
   const __amdgpu_buffer_rsrc_t ra = make_rsrc(g.A);
   const __amdgpu_buffer_rsrc_t rb = make_rsrc(g.B);
-  UnitPlan<AKC, MT, true> pa0, pa1;
-  UnitPlan<BKC, MT, false> pb0, pb1;
+  UnitPlan<AKC, true> pa0, pa1;
+  UnitPlan<BKC, false> pb0, pb1;
   pa0.init(wave, lane, g.lda, m0, g.M, 0);
   pa1.init(wave, lane, g.lda, m0, g.M, 1);
   pb0.init(wave, lane, g.ldb, n0, g.N, 0);
@@ -1429,11 +1294,11 @@ FER_DEV void tile_8ph(const GemmArgs& g, const EpiArgs& e, int bid, char* smem, 
   auto iB0 = [&](int T) { pb0.issue(rb, unit(T, 2), wave, g.ldb, kt(T), kend, kt(T) == ktail); };
   auto iB1 = [&](int T) { pb1.issue(rb, unit(T, 3), wave, g.ldb, kt(T), kend, kt(T) == ktail); };
 
-  AccT acc[FN][FM];
+  f32x4 acc[FN][FM];
 #pragma unroll
   for (int i = 0; i < FN; ++i)
 #pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = AccT{};
+    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{};
   bf16x8 fa[2][KS][QJ], fb[2][KS][QI];
 
   int claimed = -1;
@@ -1468,7 +1333,7 @@ FER_DEV void tile_8ph(const GemmArgs& g, const EpiArgs& e, int bid, char* smem, 
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk)
 #pragma unroll
-          for (int i = 0; i < QI; ++i) fb[q][kk][i] = read_frag<MT, 128, BKC, 64>(ub, wc * 32 + i * MT, kk, lane);
+          for (int i = 0; i < QI; ++i) fb[q][kk][i] = read_frag<128, BKC, 64>(ub, wc * 32 + i * MT, kk, lane);
       }
       if ((q == 0 && T == 0) || q == 2 || (q == 3 && n1)) {
         const int qa = q == 2 ? 1 : 0;
@@ -1476,7 +1341,7 @@ FER_DEV void tile_8ph(const GemmArgs& g, const EpiArgs& e, int bid, char* smem, 
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk)
 #pragma unroll
-          for (int j = 0; j < QJ; ++j) fa[qa][kk][j] = read_frag<MT, 128, AKC, 64>(ua, wr * 64 + j * MT, kk, lane);
+          for (int j = 0; j < QJ; ++j) fa[qa][kk][j] = read_frag<128, AKC, 64>(ua, wr * 64 + j * MT, kk, lane);
       }
       if (q == 0) {
         if (n1) { iB0(T + 1); wait_vm<4>(); } else { wait_vm<0>(); }
@@ -1503,7 +1368,7 @@ FER_DEV void tile_8ph(const GemmArgs& g, const EpiArgs& e, int bid, char* smem, 
         for (int j = 0; j < QJ; ++j)
 #pragma unroll
           for (int i = 0; i < QI; ++i)
-            acc[qn * QI + i][qm * QJ + j] = mfma<MT>(fb[qn][kk][i], fa[qm][kk][j], acc[qn * QI + i][qm * QJ + j]);
+            acc[qn * QI + i][qm * QJ + j] = mfma(fb[qn][kk][i], fa[qm][kk][j], acc[qn * QI + i][qm * QJ + j]);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       if (T < 16) FER_STAMP(st_i + 3);
@@ -1514,10 +1379,10 @@ FER_DEV void tile_8ph(const GemmArgs& g, const EpiArgs& e, int bid, char* smem, 
   if (nk > 0 && !wr) __builtin_amdgcn_s_barrier();  // waves 0-3 catch up with the stagger
   FER_STAMP(2);
   static_assert(64 * (256 + 4) * 4 <= 2 * BUF, "epilogue staging (2 chunks per half) must fit");
-  if constexpr (EK != EPI_GEN && MT == 16)
+  if constexpr (EK != EPI_GEN)
     tile_epilogue_wp<EK>(g, e, acc, smem, m0, n0, wr, wc, lane, seed);
   else
-    tile_epilogue<256, 256, 2, 4, MT, 2, 2 * BUF, EK>(g, e, acc, smem, m0, n0, ks, wr, wc, lane, seed);
+    tile_epilogue<256, 256, 2, 4, 2, 2 * BUF, EK>(g, e, acc, smem, m0, n0, ks, wr, wc, lane, seed);
   FER_STAMP(3);
 #ifdef FER_GEMM_STAMPS
   if (st_on) {
@@ -1527,7 +1392,7 @@ FER_DEV void tile_8ph(const GemmArgs& g, const EpiArgs& e, int bid, char* smem, 
 #endif
 }
 
-// ---- Pipelined schedule for the plain kind (EPI_STORE, MT 16): a tile's epilogue overlaps the next
+// ---- Pipelined schedule for the plain kind (EPI_STORE): a tile's epilogue overlaps the next
 // tile's first operand loads and its own store drain overlaps the next tile's first K-tile.
 // vmcnt retires in issue order, so in the plain schedule (epilogue stores, then the next tile's
 // prologue DMA and its wait) every tile start waits for the previous tile's stores to reach memory
@@ -1568,7 +1433,7 @@ constexpr bool pp_kind() {
 // for its bias loads would otherwise merge the issue and no-issue paths into a
 // vmcnt(0), i.e. wait for this DMA): bid < 0 (no next tile) or units beyond K go to FER_OOB, whose
 // LDS writes land in stage 0 and stage 1's A0 unit, which the epilogue does not use.
-template <bool AKC, bool BKC, int MT, int EK>
+template <bool AKC, bool BKC, int EK>
 FER_DEV void pro_8ph(const GemmArgs& g, int bid, char* smem, int wave, int lane) {
   constexpr int UNIT = 16384, BUF = 4 * UNIT;
   int tm, tn;
@@ -1576,8 +1441,8 @@ FER_DEV void pro_8ph(const GemmArgs& g, int bid, char* smem, int wave, int lane)
   const int kbeg = blockIdx.y * g.k_chunk, kend = bid < 0 ? kbeg : min(g.K, kbeg + g.k_chunk);
   const int ktail = kbeg + ((kend - kbeg + 63) / 64 - 1) * 64;
   const __amdgpu_buffer_rsrc_t ra = make_rsrc(g.A), rb = make_rsrc(g.B);
-  UnitPlan<AKC, MT, true> a0, a1;
-  UnitPlan<BKC, MT, false> b0, b1;
+  UnitPlan<AKC, true> a0, a1;
+  UnitPlan<BKC, false> b0, b1;
   a0.init(wave, lane, g.lda, tm * 256, g.M, 0);
   a1.init(wave, lane, g.lda, tm * 256, g.M, 1);
   b0.init(wave, lane, g.ldb, tn * 256, g.N, 0);
@@ -1604,7 +1469,7 @@ struct PpEpi {
   long ldc;
   float alpha;
 };
-template <bool AKC, bool BKC, int MT>
+template <bool AKC, bool BKC>
 FER_DEV void epi_8ph_pp(const GemmArgs& g, const PpEpi& e, f32x4 (&acc)[4][8], char* smem, int m0, int n0, int wave,
                         int lane, int next) {
   constexpr int UNIT = 16384, BUF = 4 * UNIT;
@@ -1616,7 +1481,7 @@ FER_DEV void epi_8ph_pp(const GemmArgs& g, const PpEpi& e, f32x4 (&acc)[4][8], c
   const uint32_t boff = (e.bias && nok) ? (uint32_t)n * 4 : FER_OOB;
   const f32x4 b0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rbias, boff, 0, 0));
   const f32x4 b1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rbias, boff + 16, 0, 0));
-  pro_8ph<AKC, BKC, MT, EPI_STORE>(g, next, smem, wave, lane);
+  pro_8ph<AKC, BKC, EPI_STORE>(g, next, smem, wave, lane);
   const __amdgpu_buffer_rsrc_t rc = make_rsrc(e.c);
   const uint32_t ldcb = (uint32_t)e.ldc * 2;
   const float alpha = e.alpha;
@@ -1644,9 +1509,9 @@ FER_DEV void epi_8ph_pp(const GemmArgs& g, const PpEpi& e, f32x4 (&acc)[4][8], c
 // One tile of the pipelined schedule; returns the workgroup's next tile (-1: none). PEND: the
 // previous tile's epilogue sits between this tile's prologue DMA and its first wait (every tile
 // but a workgroup's first; a template flag: as a loop-carried bool it took a VGPR that spilled).
-template <bool AKC, bool BKC, int MT, int EK, bool PEND, typename EP>
+template <bool AKC, bool BKC, int EK, bool PEND, typename EP>
 FER_DEV int tile_8ph_pp(const GemmArgs& g, const EP& e, int bid, char* smem, lds_vint* slot) {
-  static_assert(MT == 16 && pp_kind<EK>(), "pipelined schedule: MT 16 fragments, the pipelined kinds");
+  static_assert(pp_kind<EK>(), "pipelined schedule: the pipelined kinds only");
   constexpr int UNIT = 16384, BUF = 4 * UNIT;
   constexpr int FM = 8, FN = 4, QJ = 4, QI = 2, KS = 2;
   constexpr int SV = pp_sv<EK>();
@@ -1667,8 +1532,8 @@ FER_DEV int tile_8ph_pp(const GemmArgs& g, const EP& e, int bid, char* smem, lds
 
   const __amdgpu_buffer_rsrc_t ra = make_rsrc(g.A);
   const __amdgpu_buffer_rsrc_t rb = make_rsrc(g.B);
-  UnitPlan<AKC, MT, true> pa0, pa1;
-  UnitPlan<BKC, MT, false> pb0, pb1;
+  UnitPlan<AKC, true> pa0, pa1;
+  UnitPlan<BKC, false> pb0, pb1;
   pa0.init(wave, lane, g.lda, m0, g.M, 0);
   pa1.init(wave, lane, g.lda, m0, g.M, 1);
   pb0.init(wave, lane, g.ldb, n0, g.N, 0);
@@ -1717,7 +1582,7 @@ FER_DEV int tile_8ph_pp(const GemmArgs& g, const EP& e, int bid, char* smem, lds
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk)
 #pragma unroll
-          for (int i = 0; i < QI; ++i) fb[q][kk][i] = read_frag<MT, 128, BKC, 64>(ub, wc * 32 + i * MT, kk, lane);
+          for (int i = 0; i < QI; ++i) fb[q][kk][i] = read_frag<128, BKC, 64>(ub, wc * 32 + i * MT, kk, lane);
       }
       if ((q == 0 && T == 0) || q == 2 || (q == 3 && n1)) {
         const int qa = q == 2 ? 1 : 0;
@@ -1725,7 +1590,7 @@ FER_DEV int tile_8ph_pp(const GemmArgs& g, const EP& e, int bid, char* smem, lds
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk)
 #pragma unroll
-          for (int j = 0; j < QJ; ++j) fa[qa][kk][j] = read_frag<MT, 128, AKC, 64>(ua, wr * 64 + j * MT, kk, lane);
+          for (int j = 0; j < QJ; ++j) fa[qa][kk][j] = read_frag<128, AKC, 64>(ua, wr * 64 + j * MT, kk, lane);
       }
       if (q == 0) {
         if (n1) {
@@ -1755,7 +1620,7 @@ FER_DEV int tile_8ph_pp(const GemmArgs& g, const EP& e, int bid, char* smem, lds
         for (int j = 0; j < QJ; ++j)
 #pragma unroll
           for (int i = 0; i < QI; ++i)
-            acc[qn * QI + i][qm * QJ + j] = mfma<MT>(fb[qn][kk][i], fa[qm][kk][j], acc[qn * QI + i][qm * QJ + j]);
+            acc[qn * QI + i][qm * QJ + j] = mfma(fb[qn][kk][i], fa[qm][kk][j], acc[qn * QI + i][qm * QJ + j]);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
@@ -1777,7 +1642,7 @@ FER_DEV int tile_8ph_pp(const GemmArgs& g, const EP& e, int bid, char* smem, lds
     if (next >= g.tiles_m * g.tiles_n) next = -1;
   }
 
-  epi_8ph_pp<AKC, BKC, MT>(g, e, acc, smem, m0, n0, wave, lane, next);
+  epi_8ph_pp<AKC, BKC>(g, e, acc, smem, m0, n0, wave, lane, next);
   return next;
 }
 
@@ -1789,23 +1654,23 @@ FER_DEV int tile_8ph_pp(const GemmArgs& g, const EP& e, int bid, char* smem, lds
 // XCD tile_of's remap gives it): the first tile is blockIdx.x, each tile claims the next one at
 // its start (tile_8ph claim_slot) and hands it on through LDS at its end. !DYN: fixed stride
 // (split-K launches, stream capture, fer_set_persistent_mode).
-template <bool AKC, bool BKC, int MT, bool DYN, int EK>
+template <bool AKC, bool BKC, bool DYN, int EK>
 __global__ __launch_bounds__(512, 1) void gemm_8ph_kernel(GemmArgs g, EpiArgs e) {
   __shared__ __attribute__((aligned(1024))) char smem[8 * 16384 + 16];
   const int ntiles = g.tiles_m * g.tiles_n;
-  if constexpr (MT == 16 && pp_kind<EK>()) {
+  if constexpr (pp_kind<EK>()) {
     lds_vint* slot = DYN ? FER_LDS_INT(smem + 8 * 16384) : nullptr;
     int bid = DYN ? wq_first(ntiles) : ((int)blockIdx.x < ntiles ? (int)blockIdx.x : -1);
     if (bid < 0) return;
     {
       int tid = threadIdx.x;
       asm volatile("" : "+v"(tid));
-      pro_8ph<AKC, BKC, MT, EK>(g, bid, smem, __builtin_amdgcn_readfirstlane(tid >> 6), tid & 63);
+      pro_8ph<AKC, BKC, EK>(g, bid, smem, __builtin_amdgcn_readfirstlane(tid >> 6), tid & 63);
     }
     auto run = [&](const auto& pe) {
-      bid = tile_8ph_pp<AKC, BKC, MT, EK, false>(g, pe, bid, smem, slot);
+      bid = tile_8ph_pp<AKC, BKC, EK, false>(g, pe, bid, smem, slot);
 #pragma unroll 1
-      while (bid >= 0) bid = tile_8ph_pp<AKC, BKC, MT, EK, true>(g, pe, bid, smem, slot);
+      while (bid >= 0) bid = tile_8ph_pp<AKC, BKC, EK, true>(g, pe, bid, smem, slot);
     };
     run(PpEpi{e.c, e.bias, (long)e.ldc, e.alpha});
   } else if constexpr (!DYN) {
@@ -1814,7 +1679,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8ph_kernel(GemmArgs g, EpiArgs e)
     const uint64_t seed = e.drop_thresh ? step_seed(e.seed) : 0;
 #pragma unroll 1
     for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-      tile_8ph<AKC, BKC, MT, EK>(g, e, bid, smem, nullptr, seed);
+      tile_8ph<AKC, BKC, EK>(g, e, bid, smem, nullptr, seed);
       bar_lds();  // every wave is done with the epilogue's LDS before the next tile's DMA
     }
   } else {
@@ -1823,7 +1688,7 @@ __global__ __launch_bounds__(512, 1) void gemm_8ph_kernel(GemmArgs g, EpiArgs e)
     int bid = wq_first(ntiles), par = 0;
 #pragma unroll 1
     while (bid >= 0) {
-      tile_8ph<AKC, BKC, MT, EK>(g, e, bid, smem, slot + par, seed);
+      tile_8ph<AKC, BKC, EK>(g, e, bid, smem, slot + par, seed);
       bar_lds();  // every wave is done with the epilogue's LDS before the next tile's DMA
       bid = __builtin_amdgcn_readfirstlane(slot[par]);
       par ^= 1;
@@ -1921,7 +1786,7 @@ struct WgGroup {
 
 template <int NST, int WN>
 __global__ __launch_bounds__(128 * WN, 1) void gemm_wgrad_group_kernel(WgGroup grp) {
-  constexpr int BM = 128, BN = 128, NW = 2 * WN, MT = 16, TM = 64, TN = 128 / WN, FM = TM / MT, FN = TN / MT;
+  constexpr int BM = 128, BN = 128, NW = 2 * WN, TM = 64, TN = 128 / WN, FM = TM / MT, FN = TN / MT;
   constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE = A_BYTES + B_BYTES;
   __shared__ __attribute__((aligned(1024))) char smem[NST * STAGE + 16];
   const int lane = threadIdx.x & 63;
@@ -1943,8 +1808,8 @@ __global__ __launch_bounds__(128 * WN, 1) void gemm_wgrad_group_kernel(WgGroup g
 
   const u32x4 ra = rsrc4(it.A);
   const u32x4 rb = rsrc4(it.B);
-  typedef DmaPlan<BM, false, NW, MT> PA;
-  typedef DmaPlan<BN, false, NW, MT> PB;
+  typedef DmaPlan<BM, false, NW> PA;
+  typedef DmaPlan<BN, false, NW> PB;
   PA pa;
   PB pb;
   pa.init(wave, lane, it.lda, m0, it.M);
@@ -1988,16 +1853,16 @@ __global__ __launch_bounds__(128 * WN, 1) void gemm_wgrad_group_kernel(WgGroup g
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-      for (int i = 0; i < FN; ++i) bfr[kk][i] = read_frag<MT, BN, false>(cur + A_BYTES, wn * TN + i * MT, kk, lane);
+      for (int i = 0; i < FN; ++i) bfr[kk][i] = read_frag<BN, false>(cur + A_BYTES, wn * TN + i * MT, kk, lane);
 #pragma unroll
-      for (int j = 0; j < FM; ++j) af[kk][j] = read_frag<MT, BM, false>(cur, wm * TM + j * MT, kk, lane);
+      for (int j = 0; j < FM; ++j) af[kk][j] = read_frag<BM, false>(cur, wm * TM + j * MT, kk, lane);
     }
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int j = 0; j < FM; ++j)
 #pragma unroll
-        for (int i = 0; i < FN; ++i) acc[i][j] = mfma<MT>(bfr[kk][i], af[kk][j], acc[i][j]);
+        for (int i = 0; i < FN; ++i) acc[i][j] = mfma(bfr[kk][i], af[kk][j], acc[i][j]);
   }
 
   // accumulator (i, j): rows m0 + wm*64 + 16j + (lane & 15), columns n0 + wn*64 + 16i + 4(lane >> 4) + 0..3
@@ -2057,16 +1922,16 @@ __global__ __launch_bounds__(128 * WN, 1) void gemm_wgrad_group_kernel(WgGroup g
 }
 
 // -------------------------------------------------------------------- launch
-template <int BM, int BN, int WM, int WN, bool AKC, bool BKC, int MT>
+// double-buffered kernel: 128 x BN tiles (BN = 128 or 64) on 2 x 2 waves
+template <int BN, bool AKC, bool BKC>
 static int launch_bf16(GemmArgs g, const EpiArgs& e, hipStream_t st) {
-  g.tiles_m = (g.M + BM - 1) / BM;
+  g.tiles_m = (g.M + 127) / 128;
   g.tiles_n = (g.N + BN - 1) / BN;
   dim3 grid(g.tiles_m * g.tiles_n, g.splits);
-#define FER_BF16K(K) \
-  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, AKC, BKC, MT, K>), grid, dim3(64 * WM * WN), 0, st, g, e)
-  // the 128^2 K-contiguous MT16 kernel (the small-grid configs: w+ latents, 48 px) also gets the
+#define FER_BF16K(K) hipLaunchKernelGGL((gemm_bf16_kernel<128, BN, 2, 2, AKC, BKC, K>), grid, dim3(256), 0, st, g, e)
+  // the K-contiguous kernel (the small-grid configs: w+ latents, 48 px) also gets the
   // fixed-flag epilogues (row operands through its LDS-DMA staging: the LDS-DMA kinds)
-  if constexpr (BM == 128 && (BN == 128 || BN == 64) && AKC && BKC && MT == 16) {
+  if constexpr (AKC && BKC) {
     int ek = g.partial ? EPI_GEN : epi_kind(e, g.M, g.N);
     if (ek == EPI_RES2) ek = EPI_RES;
     if (ek == EPI_MUL2) ek = EPI_MUL;
@@ -2085,33 +1950,25 @@ static int launch_bf16(GemmArgs g, const EpiArgs& e, hipStream_t st) {
   return 0;
 }
 
-template <int BM, int BN, int WM, int WN, bool AKC, bool BKC, int MT>
+// ring kernel: 256^2 tiles on 2 x 4 waves
+template <bool AKC, bool BKC>
 static int launch_ring(GemmArgs g, const EpiArgs& e, hipStream_t st) {
-  g.tiles_m = (g.M + BM - 1) / BM;
-  g.tiles_n = (g.N + BN - 1) / BN;
+  g.tiles_m = (g.M + 255) / 256;
+  g.tiles_n = (g.N + 255) / 256;
   dim3 grid(g.tiles_m * g.tiles_n, g.splits);
-  hipLaunchKernelGGL((gemm_ring_kernel<BM, BN, WM, WN, AKC, BKC, MT, 4>), grid, dim3(64 * WM * WN), 0, st, g, e);
+  hipLaunchKernelGGL((gemm_ring_kernel<256, 256, 2, 4, AKC, BKC>), grid, dim3(512), 0, st, g, e);
   return 0;
 }
 
-
-
-template <bool AKC, bool BKC, int MT>
+template <bool AKC, bool BKC>
 static int launch_8ph(GemmArgs g, const EpiArgs& e, hipStream_t st) {
-  // fixed-flag epilogues for the K-contiguous MT16 kernel (the forward and transposed-shadow dgrad path)
-  const int ek = (AKC && BKC && MT == 16 && !g.partial) ? epi_kind(e, g.M, g.N) : EPI_GEN;
+  // fixed-flag epilogues for the K-contiguous kernel (the forward and transposed-shadow dgrad path)
+  const int ek = (AKC && BKC && !g.partial) ? epi_kind(e, g.M, g.N) : EPI_GEN;
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return n > 0 ? n : 256;
-  }();
   // persistent grid: one workgroup per CU (a multiple of 8: the XCD-aware tile order)
   const int ntiles = g.tiles_m * g.tiles_n;
-  const int gx = std::min(ntiles, std::max(8, ncu / 8 * 8));
+  const int gx = std::min(ntiles, std::max(8, num_cus() / 8 * 8));
   g.tq = nullptr;
   WqArgs w{};
   if (!fixed_stride_mode() && g.splits == 1) {
@@ -2120,9 +1977,9 @@ static int launch_8ph(GemmArgs g, const EpiArgs& e, hipStream_t st) {
     for (int c = 0; c < 8; ++c) g.tq_base[c] = w.base[c];
   }
   dim3 grid(gx, g.splits);
-#define FER_8PH(DY, K) hipLaunchKernelGGL((gemm_8ph_kernel<AKC, BKC, MT, DY, K>), grid, dim3(512), 0, st, g, e)
+#define FER_8PH(DY, K) hipLaunchKernelGGL((gemm_8ph_kernel<AKC, BKC, DY, K>), grid, dim3(512), 0, st, g, e)
 #define FER_8PH_K(DY)                                  \
-  if constexpr (AKC && BKC && MT == 16) {              \
+  if constexpr (AKC && BKC) {                          \
     switch (ek) {                                      \
       case EPI_STORE: FER_8PH(DY, EPI_STORE); break;   \
       case EPI_GATE: FER_8PH(DY, EPI_GATE); break;     \
@@ -2158,43 +2015,48 @@ extern "C" int fer_debug_gemm_ep_stamps(unsigned long long* host) {
 // 128x64: 3). The 128x64 tiles win where they fill the rounds clearly better (by 0.15 at short K,
 // where their extra per-tile prologue / epilogue weighs more).
 static bool use_128x64(long t128, long t64, int K) {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return n > 0 ? n : 256;
-  }();
+  const int ncu = num_cus();
   auto fill = [](long t, long slots) { return (double)t / (double)(((t + slots - 1) / slots) * slots); };
   return fill(t64, 3L * ncu) > fill(t128, 2L * ncu) + (K < 1024 ? 0.15 : 0.0);
 }
+
+// Tile configurations, the one list behind dispatch_tile, cfg_is_256 and fer_gemm_set_config:
+// X(number, 256^2 tiles?, launcher). The numbers are those of the tuning rounds (profiles, DESIGN.md and
+// the tools name configurations by them); the ones in between were variants that measured slower and
+// were removed.
+//    3  double-buffered 128^2              5  BK=32 ring 256^2 (MN x MN weight gradients)
+//    8  8-phase 256^2                     11  double-buffered 128x64 (the MN-contiguous image swizzle
+//                                             needs >= 128-wide tiles: an MN B operand keeps 128^2)
+#define FER_TILE_CFGS(X)                              \
+  X(3, false, (launch_bf16<128, AKC, BKC>))           \
+  X(5, true, (launch_ring<AKC, BKC>))                 \
+  X(8, true, (launch_8ph<AKC, BKC>))                  \
+  X(11, false, (launch_bf16<(BKC ? 64 : 128), AKC, BKC>))
 
 static int g_forced_cfg = -1;  // fer_gemm_set_config; -1: automatic
 
 static int forced_cfg() { return g_forced_cfg; }
 
-// Tile configuration: 0..3 double-buffered (256^2 MT32, 256^2 MT16, 128^2 MT32, 128^2 MT16),
-// 4..7 BK=32 ring (same order), 8/9 the 8-phase 256^2 kernel (MT16 / MT32), 10 the ping-pong
-// 256x128 kernel (two workgroups per CU), 11 double-buffered 128x64 MT16.
-static bool cfg_is_256(int c) { return c == 0 || c == 1 || c == 4 || c == 5 || c == 8 || c == 9 || c == 10; }
+static bool cfg_known(int c) {
+#define X(ID, IS256, LAUNCH) if (c == ID) return true;
+  FER_TILE_CFGS(X)
+#undef X
+  return false;
+}
+
+static bool cfg_is_256(int c) {
+#define X(ID, IS256, LAUNCH) if (c == ID) return IS256;
+  FER_TILE_CFGS(X)
+#undef X
+  return false;
+}
 
 template <bool AKC, bool BKC>
 static int dispatch_tile(int cfg, GemmArgs g, const EpiArgs& e, hipStream_t st) {
-  switch (cfg) {
-    case 0: return launch_bf16<256, 256, 2, 4, AKC, BKC, 32>(g, e, st);
-    case 1: return launch_bf16<256, 256, 2, 4, AKC, BKC, 16>(g, e, st);
-    case 2: return launch_bf16<128, 128, 2, 2, AKC, BKC, 32>(g, e, st);
-    case 3: return launch_bf16<128, 128, 2, 2, AKC, BKC, 16>(g, e, st);
-    case 4: return launch_ring<256, 256, 2, 4, AKC, BKC, 32>(g, e, st);
-    case 5: return launch_ring<256, 256, 2, 4, AKC, BKC, 16>(g, e, st);
-    case 6: return launch_ring<128, 128, 2, 2, AKC, BKC, 32>(g, e, st);
-    case 7: return launch_ring<128, 128, 2, 2, AKC, BKC, 16>(g, e, st);
-    case 9: return launch_8ph<AKC, BKC, 32>(g, e, st);
-    case 10: return launch_pp<AKC, BKC>(g, e, st);
-    case 11:  // (the MN-contiguous image swizzle needs >= 128-wide tiles: an MN B operand keeps 128^2)
-      if constexpr (BKC) return launch_bf16<128, 64, 2, 2, AKC, BKC, 16>(g, e, st);
-      else return launch_bf16<128, 128, 2, 2, AKC, BKC, 16>(g, e, st);
-    default: return launch_8ph<AKC, BKC, 16>(g, e, st);
-  }
+#define X(ID, IS256, LAUNCH) if (cfg == ID) return LAUNCH(g, e, st);
+  FER_TILE_CFGS(X)
+#undef X
+  return set_error("gemm: unknown tile configuration");
 }
 
 int gemm_launch(const GemmDesc& d, const EpiArgs& e_in, hipStream_t st) {
@@ -2305,11 +2167,8 @@ int gemm_launch(const GemmDesc& d, const EpiArgs& e_in, hipStream_t st) {
 namespace {
 int wg_splits(int tiles, int K, int req) {
   if (req > 0) return std::min(req, 8);
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    ncu = 256;
   // two 64 KB-ring workgroups per CU: split K while the grid stays within one round of those
-  return std::max(1, std::min({2 * ncu / std::max(1, tiles), K / 1024, 8}));
+  return std::max(1, std::min({2 * num_cus() / std::max(1, tiles), K / 1024, 8}));
 }
 long wg_tiles(const fer_wgrad_item* it, int n) {
   long t = 0;
@@ -2374,10 +2233,6 @@ extern "C" int fer_wgrad_group(const fer_wgrad_item* items, int n, int splits, f
   return hip_check("wgrad_group");
 }
 
-namespace fer {
-
-}  // namespace fer
-
 int fer::set_step_ptr_gemm(const uint64_t* p) { return set_step_ptr_here(p) == hipSuccess ? 0 : -1; }
 
 extern "C" int64_t fer_gemm_colsum_ws(int M, int N) {
@@ -2385,10 +2240,9 @@ extern "C" int64_t fer_gemm_colsum_ws(int M, int N) {
   return (int64_t)std::max(fer::ceil_div(std::max(M, 1), 128), 256) * N * 4;
 }
 
-
-
 extern "C" int fer_gemm_set_config(int cfg) {
-  if (cfg < -1 || cfg > 11) return fer::set_error("gemm_set_config: cfg must be -1 (automatic) or 0..11");
+  if (cfg != -1 && !fer::cfg_known(cfg))
+    return fer::set_error("gemm_set_config: cfg must be -1 (automatic), 3, 5, 8 or 11");
   fer::g_forced_cfg = cfg;
   return 0;
 }

@@ -97,8 +97,14 @@ int64_t fer_wgrad_group_ws(const fer_wgrad_item* items, int n, int splits);
 int64_t fer_gemm_colsum_ws(int M, int N);
 
 /* Tuning/testing hook (no reference counterpart): force the bf16 GEMM tile configuration for
- * every later fer_gemm call of the process. -1 = automatic (default); 0..11 = fixed kernel
- * (see csrc/gemm.hip dispatch_tile). Results are identical up to fp32 summation order. */
+ * every later fer_gemm call of the process. Accepted values (csrc/gemm.hip FER_TILE_CFGS):
+ *   -1  automatic (default; it chooses among the four below)
+ *    3  double-buffered 128x128 tiles, two workgroups per CU
+ *    5  BK=32 ring, 256x256 tiles (the automatic choice for MN x MN weight gradients)
+ *    8  8-phase persistent kernel, 256x256 tiles
+ *   11  double-buffered 128x64 tiles, three workgroups per CU (128x128 when B is MN-contiguous)
+ * Any other value returns non-zero, sets fer_last_error and leaves the selection unchanged.
+ * Results are identical up to fp32 summation order. */
 int fer_gemm_set_config(int cfg);
 
 /* Testing / A/B hook (no reference counterpart): the persistent kernels (8-phase GEMM, persistent

@@ -40,3 +40,29 @@ def test_ctypes_table_matches_header():
     L = lib()
     assert set(SIGNATURES) == set(declared())
     assert L.fer_version().decode().startswith("fervit")
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libfervit.so not built")
+def test_gemm_set_config_accepts_only_the_kept_configurations():
+    """fer_gemm_set_config takes -1 (automatic) and the four tile configurations the library still
+    has; every removed or unknown number is an error with a message (no GPU call involved)."""
+    lib = ctypes.CDLL(LIB)
+    lib.fer_gemm_set_config.argtypes = [ctypes.c_int]
+    lib.fer_gemm_set_config.restype = ctypes.c_int
+    lib.fer_last_error.restype = ctypes.c_char_p
+    try:
+        for cfg in (0, 1, 2, 4, 6, 7, 9, 10, 12, -2):
+            assert lib.fer_gemm_set_config(cfg) != 0, cfg
+            assert lib.fer_last_error(), cfg
+        for cfg in (3, 5, 8, 11, -1):
+            assert lib.fer_gemm_set_config(cfg) == 0, cfg
+    finally:
+        lib.fer_gemm_set_config(-1)
+
+
+def test_integration_doc_names_only_declared_symbols():
+    """Every fer_* identifier INTEGRATION.md names is declared in include/fervit.h."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    known = set(re.findall(r"\bfer_[a-z0-9_]+", hdr))
+    named = set(re.findall(r"\bfer_[a-z0-9_]+", open(os.path.join(ROOT, "INTEGRATION.md")).read()))
+    assert named and not sorted(named - known), sorted(named - known)

@@ -74,7 +74,7 @@ def main():
                                             2 * M * F * D, None),
         "qkv dgrad +res (B KC, K=2304)": (lambda: ops.linear_fwd(q3, wqkvt, out=out_d, res=x), 2 * M * 3 * D * D, None),
     }
-    cfg = os.environ.get("GB_CFG")  # force one tile configuration (fer_gemm_set_config)
+    cfg = os.environ.get("GB_CFG")  # force one tile configuration (fer_gemm_set_config: 3, 5, 8 or 11)
     if cfg is not None:
         from fervit._lib import lib
 

@@ -1,6 +1,6 @@
 """Run one ViT-B GEMM a few times (PMC profiling target): GEMM_CASE=fc1 (K 768, plain) | fc2 (K 3072, plain) |
 fc1_fused (bias + GELU + dropout + pre) |
-fc1_gate (the model's fc1 forward: bias + GELU + dropout + gate, pre_gate). GEMM_CFG=<n>: force library config n (fer_gemm_set_config)."""
+fc1_gate (the model's fc1 forward: bias + GELU + dropout + gate, pre_gate). GEMM_CFG=<n>: force library config n (fer_gemm_set_config: 3, 5, 8 or 11)."""
 import os
 import sys
 

@@ -61,12 +61,6 @@ for s in $STEPS; do
       [ -n "$f" ] && python3 tools/host_gaps.py "$(dirname $f)" 3 > $OUT/${TAG}_host_gaps.txt 2>&1
       ls -la $(dirname ${f:-/tmp/x}) >> $OUT/${TAG}_host_gaps.txt 2>&1
       head -40 $OUT/${TAG}_host_gaps.txt ;;
-    wgcfg)  # weight-gradient GEMMs: the automatic config vs the 8-phase kernel (MT16 / MT32), interleaved runs
-      for c in auto 8 9 auto 8 9; do
-        if [ $c = auto ]; then unset GB_CFG; else export GB_CFG=$c; fi
-        (cd tools && GB_ONLY=wgrad timeout -k 10 200 python -u gemm_bench.py 2>&1 | grep -v amdgpu.ids) \
-          | tee -a $OUT/${TAG}_wgrad_cfg.txt || exit 1
-      done; unset GB_CFG ;;
     gbench)  # GEMM microbenchmark cases whose name contains $GB_ONLY (tools/gemm_bench.py)
       (cd tools && GB_ONLY="${GB_ONLY:-}" timeout -k 10 300 python -u gemm_bench.py 2>&1 | grep -v amdgpu.ids) \
         > $OUT/${TAG}_gemm_bench.txt || { tail -20 $OUT/${TAG}_gemm_bench.txt; exit 1; }

@@ -14,6 +14,7 @@ over rounds. Variants:
   adamwbw        FusedAdamW.step_in_backward (per-layer updates from the backward's gradient-ready hook)
   noadamcache    FusedAdamW uploads its segment table every step (the round-4 behaviour)
   lib:<k>=<v>    a library selector for the variant: attnfwd (fer_attention_set_fwd_kernel), gemmcfg
+                 (fer_gemm_set_config: 3, 5, 8 or 11)
   env:<N>=<v>    environment variable N set to v for the variant (for switches the library reads per call)
   hp             the step on a high-priority non-blocking stream (torch priority -1), weight gradients at the
                  default priority (compare with nb:base)
