@@ -41,6 +41,20 @@ class LayerCfg:
     save: bool = True
 
 
+# Optional callable(qkv, cfg) run by the encoder-layer forwards right after their qkv projection
+# (fervit.explain installs it to read attention maps). None: the launch sequence is untouched.
+ATTN_TAP = None
+
+
+def _attn_tap(qkv: torch.Tensor, cfg: LayerCfg) -> None:
+    if cfg.save or cfg.dropout > 0 or torch.cuda.is_current_stream_capturing():
+        why = ("gradients are being recorded" if cfg.save else
+               "attention dropout is on" if cfg.dropout > 0 else "the stream is being captured")
+        raise RuntimeError(f"fervit: attention maps are an eval / no-grad feature ({why}): call model.eval() and "
+                           "run the forward under torch.no_grad(), outside graph capture")
+    ATTN_TAP(qkv, cfg)
+
+
 def _weight(flat: FlatParams, p: torch.nn.Parameter, dt: torch.dtype) -> torch.Tensor:
     """Matrix operand in the compute dtype (bf16 shadow or the fp32 master)."""
     return flat.half_view(p) if dt == torch.bfloat16 else p.data
@@ -215,6 +229,8 @@ class PostNormLayerFn(torch.autograd.Function):
         seeds = [next_seed() for _ in range(4)] if pd > 0 else [0, 0, 0, 0]
         f32 = torch.float32
         qkv = ops.linear_fwd(x, _weight(flat, in_w, dt), in_b.data)
+        if ATTN_TAP is not None:
+            _attn_tap(qkv, cfg)
         o = _empty(M, D, x)
         lse = ops.attention_saved(qkv, cfg.B, cfg.N, cfg.H, dh, dropout=pd)
         ops.attention_fwd(qkv, o, lse, cfg.B, cfg.N, cfg.H, dh, dropout=pd, seed=seeds[0])
@@ -296,6 +312,8 @@ class PreNormBlockFn(torch.autograd.Function):
         r1 = torch.empty_like(m1)
         h1 = ops.layernorm_fwd(x, n1w.data, n1b.data, cfg.eps, mean=m1, rstd=r1)
         qkv = ops.linear_fwd(h1, _weight(flat, qkv_w, dt), qkv_b.data)
+        if ATTN_TAP is not None:
+            _attn_tap(qkv, cfg)
         o = _empty(M, D, x)
         lse = ops.attention_saved(qkv, cfg.B, cfg.N, cfg.H, dh)
         ops.attention_fwd(qkv, o, lse, cfg.B, cfg.N, cfg.H, dh)

@@ -247,6 +247,53 @@ def attention_bwd(qkv, out, dout, saved, dqkv, B, N, H, dh, dropout=0.0, seed=0,
     return dqkv
 
 
+def attention_probs(qkv, B, N, H, dh, *, average_heads=True, q_start=0, q_count=None, out=None):
+    """fp32 softmax(Q K^T / sqrt(dh)) of query rows q_start .. q_start+q_count-1 (default: all rows
+    from q_start) of the qkv buffer attention_fwd takes; eval semantics (no dropout).
+    average_heads: [B, q_count, N], the mean over heads (what nn.MultiheadAttention returns with
+    need_weights=True); else [B, H, q_count, N]. The per-head tensor is never written when averaging."""
+    _dev(qkv)
+    code = dcode(qkv)
+    B, N, H, dh, q_start = int(B), int(N), int(H), int(dh), int(q_start)
+    if min(B, N, H, dh) < 1:
+        raise ValueError("attention_probs: B, N, H, dh must be >= 1")
+    if qkv.dim() != 2 or qkv.shape[0] != B * N or qkv.shape[1] < 3 * H * dh or qkv.stride(1) != 1 \
+            or qkv.stride(0) < 3 * H * dh:
+        raise ValueError("attention_probs: qkv must be [B*N, >= 3*H*dh] with unit column stride")
+    nq = N - q_start if q_count is None else int(q_count)
+    if q_start < 0 or nq < 1 or q_start + nq > N:
+        raise ValueError(f"attention_probs: query rows {q_start}..{q_start + nq - 1} outside [0, {N})")
+    shape = (B, nq, N) if average_heads else (B, H, nq, N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=qkv.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != qkv.device:
+        raise ValueError(f"attention_probs: out must be a contiguous fp32 {shape} tensor on qkv's device")
+    check(lib().fer_attention_probs(code, qkv.data_ptr(), qkv.stride(0), B, N, H, dh, 1.0 / math.sqrt(dh),
+                                    int(bool(average_heads)), q_start, nq, out.data_ptr(), out.numel(), stream()),
+          "attention_probs")
+    return out
+
+
+def attention_rollout_cls(maps, residual=0.5, out=None):
+    """CLS row [B, N] of the attention rollout of head-averaged maps [L, B, N, N] (fp32):
+    row 0 of A'_L ... A'_1 with A'_l = residual * I + (1 - residual) * A_l."""
+    _dev(maps)
+    if maps.dtype != torch.float32 or maps.dim() != 4 or maps.shape[2] != maps.shape[3] or not maps.is_contiguous():
+        raise ValueError("attention_rollout_cls: maps must be a contiguous fp32 [L, B, N, N] tensor")
+    if not 0.0 <= float(residual) < 1.0:
+        raise ValueError("attention_rollout_cls: residual must be in [0, 1)")
+    L, B, N, _ = maps.shape
+    if L < 1 or B < 1 or N < 1:
+        raise ValueError("attention_rollout_cls: empty maps")
+    if out is None:
+        out = torch.empty(B, N, dtype=torch.float32, device=maps.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, N) or not out.is_contiguous() or out.device != maps.device:
+        raise ValueError("attention_rollout_cls: out must be a contiguous fp32 [B, N] tensor on maps' device")
+    check(lib().fer_attention_rollout_cls(maps.data_ptr(), L, B, N, float(residual), out.data_ptr(), stream()),
+          "attention_rollout_cls")
+    return out
+
+
 # ------------------------------------------------------------------ misc
 def colsum(x, out, accumulate=False, scale=None):
     M, N = x.shape

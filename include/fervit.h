@@ -176,6 +176,28 @@ int fer_attention_bwd(int dtype, const void* qkv, int64_t ld_qkv, const void* ou
                       uint32_t drop_thresh, float drop_scale, uint64_t seed, float* colsum, int colsum_accumulate,
                       fer_stream_t stream);
 
+/* Attention maps (eval semantics, no dropout): probs = fp32 softmax(Q K^T * scale) of the query rows
+ * q0 .. q0+nq-1 of every batch element -- what nn.MultiheadAttention(need_weights=True) returns
+ * (`image_vit.py:101`, `latent_vit.py:24` encoder layers) and what a forward hook on timm's
+ * Attention sees (hybrid); the fused forward above never materialises them. qkv: the layout
+ * fer_attention_fwd takes ([B*N][ld_qkv], q|k|v column blocks of width H*dh).
+ *   head_avg = 0: probs [B][H][nq][N];  head_avg = 1: probs [B][nq][N], the mean over heads, summed in
+ *   head order 0..H-1 inside one workgroup (deterministic, no atomics; the per-head tensor is never
+ *   written). probs_floats: capacity of probs in floats, >= B*(head_avg ? 1 : H)*nq*N.
+ * A row-selected call returns the same bits as the matching rows of a full call. No workspace:
+ * Q K^T is computed twice (max / sum pass, then normalise-and-store pass).
+ * bf16: any N >= 1, dh <= 128, dh % 8 == 0, ld_qkv % 8 == 0, qkv 16-byte aligned, H <= 128;
+ * fp32: exact parity path (plain FMA), any dh. q0 < 0, nq < 1, q0 + nq > N, a short probs buffer or an
+ * unsupported dh return a negative code and launch nothing. */
+int fer_attention_probs(int dtype, const void* qkv, int64_t ld_qkv, int B, int N, int H, int dh, float scale,
+                        int head_avg, int q0, int nq, float* probs, int64_t probs_floats, fer_stream_t stream);
+/* CLS row of the attention rollout (Abnar & Zuidema 2020) over L layers of head-averaged maps
+ * [L][B][N][N] fp32: r [B][N] = row 0 of A'_L ... A'_1, A'_l = residual*I + (1-residual)*A_l, as a
+ * chain of vector-matrix products (r = e_0; for l = L..1: r <- residual*r + (1-residual)*(r A_l)),
+ * O(L N^2). One workgroup per batch element, fixed summation order (deterministic). Any L >= 1,
+ * 1 <= N <= 7680 (r is double-buffered in LDS); residual outside [0, 1) is an error. */
+int fer_attention_rollout_cls(const float* maps, int L, int B, int N, float residual, float* r, fer_stream_t stream);
+
 /* Column sums: out[n] (+)= scale * sum_m x[m][n]  (bias gradients). ws >= fer_colsum_ws(M,N). */
 int64_t fer_colsum_ws(int M, int N);
 int fer_colsum(int dtype, const void* x, int64_t ldx, int M, int N, float* out, int accumulate,
