@@ -22,12 +22,11 @@ import pytest
 import torch
 
 from dropmask import keep_mask
+from elemwise import BF_ROUND, U, assert_bits_equal, assert_close, measure_c  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-U = 2.0 ** -23
-BF_ROUND = 2.0 ** -8
 BIG = 8192 * 256 + 3  # past the 8192-block grid cap of the element kernels: grid-stride loop
 
 
@@ -58,51 +57,6 @@ def f32v(v):
 
 def cu_count():
     return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-# ---------------------------------------------------------------------- the comparison helper
-def measure_c(op, dtype, pairs):
-    """c for one op: pairs = [(fp32-torch result, float64 ref, scale)]; worst error of the fp32 torch
-    computation in units of 2^-23 * scale, times 4, floor 16."""
-    worst = 0.0
-    for f32, ref, scale in pairs:
-        f32, ref, scale = torch.as_tensor(f32).double(), torch.as_tensor(ref).double(), torch.as_tensor(scale).double()
-        err = (f32 - ref).abs()
-        live = scale > 0
-        if live.any():
-            worst = max(worst, (err[live] / (U * scale[live])).max().item())
-        assert (err[~live] == 0).all(), f"{op}: fp32 torch differs from the reference where the scale is 0"
-    print(f"c-measure {op} {dtype} {worst:.3f}")
-    return max(16.0, 4.0 * worst)
-
-
-def assert_close(name, got, ref, scale, c, out_round):
-    got = torch.as_tensor(got).detach().double().cpu().reshape(-1)
-    ref = torch.as_tensor(ref).double()
-    scale = torch.as_tensor(scale).double().broadcast_to(ref.shape).reshape(-1)
-    ref = ref.reshape(-1)
-    assert got.shape == ref.shape == scale.shape, (name, got.shape, ref.shape, scale.shape)
-    bound = out_round * ref.abs() + c * U * scale
-    err = (got - ref).abs()
-    bad = ~(err <= bound)  # also true for NaN
-    if bad.any():
-        ratio = torch.where(bad, err / bound.clamp_min(1e-300), torch.zeros_like(err))
-        ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, float("inf")), ratio)
-        i = int(ratio.argmax())
-        raise AssertionError(
-            f"{name}: {int(bad.sum())} of {bad.numel()} elements out of bound; worst at flat index {i}: "
-            f"got {got[i].item():.9g} ref {ref[i].item():.9g} |err| {err[i].item():.3g} bound {bound[i].item():.3g} "
-            f"(c = {c:.1f}, out_round = {out_round:g})")
-
-
-def assert_bits_equal(name, a, b):
-    ia = a.contiguous().view(torch.int16 if a.element_size() == 2 else torch.int32)
-    ib = b.contiguous().view(torch.int16 if b.element_size() == 2 else torch.int32)
-    ne = (ia != ib).reshape(-1)
-    if ne.any():
-        i = int(ne.nonzero()[0])
-        raise AssertionError(f"{name}: {int(ne.sum())} elements differ bit-wise, first at flat index {i}: "
-                             f"{a.reshape(-1)[i].item()!r} vs {b.reshape(-1)[i].item()!r}")
 
 
 # ---------------------------------------------------------------------- LayerNorm references
