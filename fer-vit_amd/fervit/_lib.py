@@ -82,6 +82,16 @@ SIGNATURES = {
     "fer_head_bwd_ws": (i64, [i32, i32, i32]),
     "fer_head_bwd": (i32, [i32, vp, i64, fp, fp, fp, fp, fp, vp, i32, i32, i32, fp, fp, fp, fp, i32, i32, i32, i32,
                            u32, f32, u64, fp, i64, vp]),
+    "fer_conv1d_cols": (i32, [i32, vp, i64, vp, i64, i32, i32, i32, vp]),
+    "fer_conv1d_cols_bwd": (i32, [i32, vp, i64, vp, i64, vp, i64, i32, i32, i32, vp]),
+    "fer_batchnorm_fwd": (i32, [i32, vp, i64, fp, fp, fp, fp, vp, i32, f32, f32, vp, i64, i32, u32, f32, u64, vp, i64,
+                                fp, fp, i32, i32, vp]),
+    "fer_batchnorm_bwd": (i32, [i32, vp, i64, vp, i64, fp, fp, fp, fp, vp, i64, i32, u32, f32, u64, i32, vp, i64, vp,
+                                i64, fp, fp, i32, i32, i32, vp]),
+    "fer_seq_mean_fwd": (i32, [i32, vp, i64, vp, i64, i32, i32, i32, vp]),
+    "fer_seq_mean_bwd": (i32, [i32, vp, i64, vp, i64, i32, i32, i32, vp]),
+    "fer_logits_fwd": (i32, [i32, vp, i64, fp, fp, fp, i32, i32, i32, vp]),
+    "fer_logits_bwd": (i32, [i32, vp, i64, fp, fp, vp, i64, vp, i64, fp, fp, i32, i32, i32, i32, vp]),
     "fer_cross_entropy": (i32, [fp, vp, fp, i32, i32, f32, f32, fp, fp, vp]),
     "fer_wplus_ws": (i64, [i32, i32, i32]),
     "fer_wplus_fwd": (i32, [fp, fp, i32, i32, i32, fp, fp, vp, fp, fp, fp, fp, f32, fp, vp]),

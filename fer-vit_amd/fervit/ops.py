@@ -397,3 +397,120 @@ def dropout(x, p, seed):
     check(lib().fer_dropout(dcode(x), x.data_ptr(), out.data_ptr(), x.numel(), thr, sc, seed & (2**64 - 1), stream()),
           "dropout")
     return out
+
+
+# ------------------------------------------------------------------ LatentCNN operators (csrc/convbn.hip)
+def _rows(t: torch.Tensor, what: str) -> None:
+    _dev(t)
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{what}: [rows, cols] tensors with unit column stride")
+
+
+def conv1d_cols(x, B, L, out=None):
+    """im2col of nn.Conv1d(k=3, padding=1): x [B*L, C] -> cols [B*L, 3*C] in (cin, k) column order."""
+    _rows(x, "conv1d_cols")
+    M, Cc = x.shape
+    if M != B * L:
+        raise ValueError("conv1d_cols: x must have B*L rows")
+    out = torch.empty(M, 3 * Cc, dtype=x.dtype, device=x.device) if out is None else out
+    check(lib().fer_conv1d_cols(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), B, L, Cc,
+                                stream()), "conv1d_cols")
+    return out
+
+
+def conv1d_cols_bwd(dcols, B, L, out=None, res=None):
+    """dx [B*L, C] from dcols [B*L, 3*C] (the adjoint of conv1d_cols), plus `res` [B*L, C] when given."""
+    _rows(dcols, "conv1d_cols_bwd")
+    M, K = dcols.shape
+    if M != B * L or K % 3:
+        raise ValueError("conv1d_cols_bwd: dcols must be [B*L, 3*C]")
+    out = torch.empty(M, K // 3, dtype=dcols.dtype, device=dcols.device) if out is None else out
+    check(lib().fer_conv1d_cols_bwd(dcode(dcols), dcols.data_ptr(), dcols.stride(0), ptr(res),
+                                    K // 3 if res is None else res.stride(0), out.data_ptr(), out.stride(0),
+                                    B, L, K // 3, stream()), "conv1d_cols_bwd")
+    return out
+
+
+def batchnorm_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked, train, momentum=0.1, eps=1e-5,
+                  res=None, relu=False, dropout=0.0, seed=0, out=None, mean=None, rstd=None):
+    """y = dropout(relu?(BatchNorm(x) (+ res))) over the rows of x [M, C]; train: batch statistics and the
+    running-statistic update on the device, else the running statistics. Returns (y, mean, rstd)."""
+    _rows(x, "batchnorm_fwd")
+    M, Cc = x.shape
+    if train and M < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    out = torch.empty_like(x) if out is None else out
+    mean = torch.empty(Cc, dtype=torch.float32, device=x.device) if mean is None else mean
+    rstd = torch.empty(Cc, dtype=torch.float32, device=x.device) if rstd is None else rstd
+    thr, sc = drop_args(dropout)
+    check(lib().fer_batchnorm_fwd(dcode(x), x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(),
+                                  ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), int(bool(train)),
+                                  momentum, eps, ptr(res), Cc if res is None else res.stride(0), int(bool(relu)), thr,
+                                  sc, seed & (2**64 - 1), out.data_ptr(), out.stride(0), mean.data_ptr(),
+                                  rstd.data_ptr(), M, Cc, stream()), "batchnorm_fwd")
+    return out, mean, rstd
+
+
+def batchnorm_bwd(dy, x, mean, rstd, gamma, beta, train, res=None, relu=False, dropout=0.0, seed=0, dx=None,
+                  dres=None, dgamma=None, dbeta=None, accumulate=False):
+    """(dx, dres) of batchnorm_fwd; dgamma / dbeta (fp32 [C], optional) receive or accumulate the parameter
+    gradients. dres: pass a tensor to receive the gated gradient of the residual branch."""
+    _rows(x, "batchnorm_bwd")
+    M, Cc = x.shape
+    if dx is None:
+        dx = torch.empty_like(x)
+    thr, sc = drop_args(dropout)
+    check(lib().fer_batchnorm_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), mean.data_ptr(),
+                                  rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ptr(res),
+                                  Cc if res is None else res.stride(0), int(bool(relu)), thr, sc, seed & (2**64 - 1),
+                                  int(bool(train)), ptr(dx), Cc if dx is None else dx.stride(0), ptr(dres),
+                                  Cc if dres is None else dres.stride(0), ptr(dgamma), ptr(dbeta), int(accumulate),
+                                  M, Cc, stream()), "batchnorm_bwd")
+    return dx, dres
+
+
+def seq_mean_fwd(x, B, L, out=None):
+    """[B*L, C] -> [B, C], the mean over the L rows of each sample."""
+    _rows(x, "seq_mean_fwd")
+    if x.shape[0] != B * L:
+        raise ValueError("seq_mean_fwd: x must have B*L rows")
+    Cc = x.shape[1]
+    out = torch.empty(B, Cc, dtype=x.dtype, device=x.device) if out is None else out
+    check(lib().fer_seq_mean_fwd(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), B, L, Cc,
+                                 stream()), "seq_mean_fwd")
+    return out
+
+
+def seq_mean_bwd(dy, B, L, out=None):
+    _rows(dy, "seq_mean_bwd")
+    if dy.shape[0] != B:
+        raise ValueError("seq_mean_bwd: dy must have B rows")
+    Cc = dy.shape[1]
+    out = torch.empty(B * L, Cc, dtype=dy.dtype, device=dy.device) if out is None else out
+    check(lib().fer_seq_mean_bwd(dcode(dy), dy.data_ptr(), dy.stride(0), out.data_ptr(), out.stride(0), B, L, Cc,
+                                 stream()), "seq_mean_bwd")
+    return out
+
+
+def logits_fwd(x, W, bias=None, out=None):
+    """fp32 logits [B, C] = x [B, D] W^T + bias for a small C (W [C, D], bias fp32)."""
+    _rows(x, "logits_fwd")
+    B, D = x.shape
+    Cc = W.shape[0]
+    out = torch.empty(B, Cc, dtype=torch.float32, device=x.device) if out is None else out
+    check(lib().fer_logits_fwd(dcode(x), x.data_ptr(), x.stride(0), W.data_ptr(), ptr(bias), out.data_ptr(), B, D, Cc,
+                               stream()), "logits_fwd")
+    return out
+
+
+def logits_bwd(x, W, dlogits, gate=None, dx=None, dW=None, dbias=None, accumulate=False, want_dx=True):
+    """dx [B, D] (x's dtype, times `gate` when given); dW / dbias (fp32, optional) receive or accumulate."""
+    _rows(x, "logits_bwd")
+    B, D = x.shape
+    Cc = W.shape[0]
+    if dx is None and want_dx:
+        dx = torch.empty_like(x)
+    check(lib().fer_logits_bwd(dcode(x), x.data_ptr(), x.stride(0), W.data_ptr(), dlogits.data_ptr(), ptr(gate),
+                               D if gate is None else gate.stride(0), ptr(dx), D if dx is None else dx.stride(0),
+                               ptr(dW), ptr(dbias), int(accumulate), B, D, Cc, stream()), "logits_bwd")
+    return dx

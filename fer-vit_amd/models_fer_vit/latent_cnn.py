@@ -1,0 +1,225 @@
+"""LatentCNN baseline (reference `models_fer_vit/latent_cnn.py`): 1-D CNNs over StyleGAN w+ codes,
+input (B, 18, 512) -> logits (B, 7), the CNN arm of the reference's cnn_vs_vit experiments.
+
+Same constructors, attributes, initialisation order and state_dict keys as the reference (the
+modules below are the reference's nn.Conv1d / nn.BatchNorm1d / nn.Linear containers, built in the
+same order so the default and custom initialisers consume the RNG identically); the forward runs
+on the HIP path (fervit/cnn.py) in token-major layout [B*L][C]. BatchNorm's running_mean,
+running_var and num_batches_tracked are ordinary module buffers, updated on the device.
+
+`create_latent_cnn('standard')` (`latent_cnn.py:66-161`, the trainer's default) and `'light'`
+(`:264-330`) are native. `'deep'` needs a softmax attention pooling and `'2d'` needs Conv2d /
+MaxPool2d / Dropout2d kernels, which the library does not have: they raise NotImplementedError.
+"""
+import torch
+import torch.nn as nn
+
+from fervit import ops
+from fervit.cnn import CnnCfg, ConvBNFn, LogitsFn, MlpLogitsFn, ResBlockFn, SeqMeanFn, bn_state
+from fervit.module import FerModule
+
+
+def _p(drop, training: bool) -> float:
+    return float(drop.p) if (drop is not None and training) else 0.0
+
+
+def _check_conv(conv: nn.Conv1d) -> None:
+    if conv.kernel_size != (3,) or conv.stride != (1,) or conv.padding != (1,) or conv.dilation != (1,) \
+            or conv.groups != 1 or conv.padding_mode != "zeros":
+        raise NotImplementedError("fervit: only Conv1d(kernel_size=3, stride=1, padding=1) has a kernel")
+
+
+def _rows(x: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
+    """(B, L, D) -> token-major [B*L][D] in the compute dtype."""
+    B, L, D = x.shape
+    t = x.reshape(B * L, D)
+    if x.requires_grad and torch.is_grad_enabled():
+        return t.to(dt).contiguous()
+    t = t.contiguous().float()
+    return ops.cast_bf16(t) if dt == torch.bfloat16 else t
+
+
+def _from_channels_first(x: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
+    return _rows(x.transpose(1, 2), dt)
+
+
+class LatentConv1D(FerModule):
+    """Conv1d -> BatchNorm1d -> ReLU -> Dropout (`latent_cnn.py:14-38`)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dropout=0.2):
+        super().__init__()
+        self.conv = nn.Conv1d(in_channels, out_channels, kernel_size, stride, padding, bias=False)
+        self.bn = nn.BatchNorm1d(out_channels)
+        self.relu = nn.ReLU(inplace=True)
+        self.dropout = nn.Dropout(dropout) if dropout > 0 else None
+
+    def run_rows(self, t, B, L, flat, save):
+        _check_conv(self.conv)
+        cfg = CnnCfg(B, L, True, True, _p(self.dropout, self.training), save)
+        return ConvBNFn.apply(t, None, cfg, flat, bn_state(self.bn), self.conv.weight, self.conv.bias,
+                              self.bn.weight, self.bn.bias)
+
+    def forward(self, x):
+        """x: (B, C, L), as the reference; returns (B, Cout, L) in x's dtype."""
+        B, _, L = x.shape
+        flat = self.fer_flat()
+        y = self.run_rows(_from_channels_first(x, self.compute_dtype()), B, L, flat,
+                          self.need_grad(x, list(self.parameters())))
+        return y.view(B, L, -1).transpose(1, 2).to(x.dtype)
+
+
+class LatentResBlock1D(FerModule):
+    """relu(bn2(conv2(drop(relu(bn1(conv1 x))))) + x) (`latent_cnn.py:41-63`)."""
+
+    def __init__(self, channels, kernel_size=3, dropout=0.2):
+        super().__init__()
+        padding = kernel_size // 2
+        self.conv1 = nn.Conv1d(channels, channels, kernel_size, padding=padding, bias=False)
+        self.bn1 = nn.BatchNorm1d(channels)
+        self.conv2 = nn.Conv1d(channels, channels, kernel_size, padding=padding, bias=False)
+        self.bn2 = nn.BatchNorm1d(channels)
+        self.dropout = nn.Dropout(dropout) if dropout > 0 else None
+
+    def run_rows(self, t, B, L, flat, save):
+        _check_conv(self.conv1)
+        _check_conv(self.conv2)
+        cfg = CnnCfg(B, L, True, True, _p(self.dropout, self.training), save)
+        return ResBlockFn.apply(t, cfg, flat, bn_state(self.bn1), bn_state(self.bn2), self.conv1.weight,
+                                self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias)
+
+    def forward(self, x):
+        B, _, L = x.shape
+        flat = self.fer_flat()
+        y = self.run_rows(_from_channels_first(x, self.compute_dtype()), B, L, flat,
+                          self.need_grad(x, list(self.parameters())))
+        return y.view(B, L, -1).transpose(1, 2).to(x.dtype)
+
+
+def _init_weights(model: nn.Module) -> None:
+    """`latent_cnn.py:125-136` (and `:309-319`)."""
+    for m in model.modules():
+        if isinstance(m, nn.Conv1d):
+            nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        elif isinstance(m, nn.BatchNorm1d):
+            nn.init.constant_(m.weight, 1)
+            nn.init.constant_(m.bias, 0)
+        elif isinstance(m, nn.Linear):
+            nn.init.normal_(m.weight, 0, 0.01)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+
+
+class LatentCNN(FerModule):
+    """(B, 18, 512) -> conv blocks -> residual blocks -> mean over the sequence -> classifier
+    (`latent_cnn.py:66-161`)."""
+
+    def __init__(self, latent_dim: int = 512, seq_len: int = 18, num_classes: int = 7,
+                 hidden_dims: list = [512, 512, 512, 512], dropout: float = 0.3, use_residual: bool = True):
+        super().__init__()
+        self.latent_dim = latent_dim
+        self.seq_len = seq_len
+        self.use_residual = use_residual
+        layers = []
+        in_ch = latent_dim
+        for hidden_dim in hidden_dims:
+            layers.append(LatentConv1D(in_ch, hidden_dim, kernel_size=3, dropout=dropout))
+            in_ch = hidden_dim
+        self.conv_layers = nn.Sequential(*layers)
+        if use_residual:
+            self.res_blocks = nn.ModuleList([LatentResBlock1D(hidden_dims[-1], kernel_size=3, dropout=dropout)
+                                             for _ in range(2)])
+        self.global_avg_pool = nn.AdaptiveAvgPool1d(1)
+        self.use_max_pool = False
+        self.classifier = nn.Sequential(
+            nn.Flatten(),
+            nn.Linear(hidden_dims[-1], 512),
+            nn.BatchNorm1d(512),
+            nn.ReLU(inplace=True),
+            nn.Dropout(dropout),
+            nn.Linear(512, num_classes),
+        )
+        self._init_weights()
+
+    def _init_weights(self):
+        _init_weights(self)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: (B, seq_len, latent_dim) -> logits (B, num_classes), fp32."""
+        B, L, _ = x.shape
+        flat = self.fer_flat()
+        save = self.need_grad(x, list(self.parameters()))
+        t = _rows(x, self.compute_dtype())
+        for blk in self.conv_layers:
+            t = blk.run_rows(t, B, L, flat, save)
+        if self.use_residual:
+            for blk in self.res_blocks:
+                t = blk.run_rows(t, B, L, flat, save)
+        pooled = SeqMeanFn.apply(t, B, L)
+        _, lin1, bn, _, drop, lin2 = self.classifier
+        cfg = CnnCfg(B, 1, False, True, _p(drop, self.training), save)
+        h = ConvBNFn.apply(pooled, None, cfg, flat, bn_state(bn), lin1.weight, lin1.bias, bn.weight, bn.bias)
+        return LogitsFn.apply(h, save, flat, lin2.weight, lin2.bias)
+
+
+class LatentCNNLight(FerModule):
+    """Three biased conv + BN + ReLU stages, mean pool, two-layer classifier (`latent_cnn.py:264-330`)."""
+
+    def __init__(self, latent_dim: int = 512, seq_len: int = 18, num_classes: int = 7, dropout: float = 0.3):
+        super().__init__()
+        self.encoder = nn.Sequential(
+            nn.Conv1d(latent_dim, 256, kernel_size=3, padding=1),
+            nn.BatchNorm1d(256),
+            nn.ReLU(inplace=True),
+            nn.Dropout(dropout),
+            nn.Conv1d(256, 256, kernel_size=3, padding=1),
+            nn.BatchNorm1d(256),
+            nn.ReLU(inplace=True),
+            nn.Dropout(dropout),
+            nn.Conv1d(256, 384, kernel_size=3, padding=1),
+            nn.BatchNorm1d(384),
+            nn.ReLU(inplace=True),
+        )
+        self.pool = nn.AdaptiveAvgPool1d(1)
+        self.classifier = nn.Sequential(
+            nn.Flatten(),
+            nn.Linear(384, 256),
+            nn.ReLU(inplace=True),
+            nn.Dropout(dropout),
+            nn.Linear(256, num_classes),
+        )
+        self._init_weights()
+
+    def _init_weights(self):
+        _init_weights(self)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        B, L, _ = x.shape
+        flat = self.fer_flat()
+        save = self.need_grad(x, list(self.parameters()))
+        t = _rows(x, self.compute_dtype())
+        enc = self.encoder
+        for ci, di in ((0, 3), (4, 7), (8, None)):
+            conv, bn = enc[ci], enc[ci + 1]
+            _check_conv(conv)
+            cfg = CnnCfg(B, L, True, True, _p(enc[di] if di is not None else None, self.training), save)
+            t = ConvBNFn.apply(t, None, cfg, flat, bn_state(bn), conv.weight, conv.bias, bn.weight, bn.bias)
+        pooled = SeqMeanFn.apply(t, B, L)
+        _, lin1, _, drop, lin2 = self.classifier
+        return MlpLogitsFn.apply(pooled, _p(drop, self.training), save, flat, lin1.weight, lin1.bias, lin2.weight,
+                                 lin2.bias)
+
+
+def create_latent_cnn(model_type: str = "standard", latent_dim: int = 512, seq_len: int = 18, num_classes: int = 7,
+                      dropout: float = 0.3):
+    """`latent_cnn.py:412-438`. 'light' and 'standard' run on the HIP path."""
+    if model_type == "light":
+        return LatentCNNLight(latent_dim, seq_len, num_classes, dropout)
+    if model_type == "standard":
+        return LatentCNN(latent_dim, seq_len, num_classes, dropout=dropout, use_residual=True)
+    if model_type == "deep":
+        raise NotImplementedError("create_latent_cnn('deep'): LatentCNNDeep pools with a softmax attention over the "
+                                  "sequence (Conv1d(512, 1, 1) + Softmax + weighted sum), which has no kernel here")
+    if model_type == "2d":
+        raise NotImplementedError("create_latent_cnn('2d'): LatentCNN2D needs Conv2d(3x3), MaxPool2d and Dropout2d "
+                                  "kernels, which the library does not have")
+    raise ValueError(f"Unknown model type: {model_type}")

@@ -247,6 +247,67 @@ int fer_head_bwd(int dtype, const void* t, int64_t row_stride, const float* ln_w
                  uint32_t drop_thresh, float drop_scale, uint64_t seed, float* ws, int64_t ws_bytes,
                  fer_stream_t stream);
 
+/* ---- LatentCNN baseline (`models_fer_vit/latent_cnn.py`), csrc/convbn.hip. Token-major [M = B*L][C]:
+ * the reference's x.transpose(1, 2) (`latent_cnn.py:146,326`) is free and BatchNorm's channel axis is the
+ * column axis. Rows are moved in 16-byte pieces: C (3*C for cols) must be a multiple of 8 (bf16) or 4
+ * (fp32), row strides likewise, base pointers 16-byte aligned. A rejected call launches nothing. */
+
+/* nn.Conv1d(kernel_size=3, padding=1, stride=1) (`latent_cnn.py:22-23,49,51,282,287,292`) as im2col
+ * around fer_gemm: cols[b*L + l][cin*3 + k] = x[b*L + l + k - 1][cin] for 0 <= l + k - 1 < L, else 0
+ * (never the neighbouring sample); dtype in = dtype out, values copied bit for bit. The (cin, k) column
+ * order is the memory order of nn.Conv1d.weight [Cout][Cin][3], so the parameter (and its bf16 shadow)
+ * is fer_gemm's B operand with K = 3*Cin as it stands and the weight gradient lands in its own layout. */
+int fer_conv1d_cols(int dtype, const void* x, int64_t ldx, void* cols, int64_t ldc, int B, int L, int C,
+                    fer_stream_t stream);
+/* Its adjoint: dx[b*L + l][c] = (res[b*L + l][c] +) sum_k dcols[b*L + l - k + 1][c*3 + k] over
+ * 0 <= l - k + 1 < L. res (optional): the gradient arriving over a residual connection
+ * (LatentResBlock1D `latent_cnn.py:56,61`), added first. */
+int fer_conv1d_cols_bwd(int dtype, const void* dcols, int64_t ldd, const void* res, int64_t ldr, void* dx,
+                        int64_t lddx, int B, int L, int C, fer_stream_t stream);
+
+/* nn.BatchNorm1d over the M rows of x [M][C] (`latent_cnn.py:24,50,52,117,283,288,293`), fp32
+ * statistics, with the model's epilogues fused: y = dropout(relu?(gamma * xhat + beta (+ res))).
+ * train != 0: per-channel mean and biased variance of this call's rows (two passes: mean, then squared
+ * deviations), running_mean / running_var (optional) updated on the device with `momentum` and the
+ * unbiased variance M/(M-1), *num_batches_tracked (optional, int64) += 1; needs M >= 2.
+ * train == 0: normalises with running_mean / running_var (required), updates nothing.
+ * mean / rstd (optional, [C] fp32) receive the statistics used, for the backward. relu: 0 / 1. res
+ * optional (LatentResBlock1D `latent_cnn.py:60-62`). No workspace; repeat calls are bit-identical. */
+int fer_batchnorm_fwd(int dtype, const void* x, int64_t ldx, const float* gamma, const float* beta,
+                      float* running_mean, float* running_var, int64_t* num_batches_tracked, int train,
+                      float momentum, float eps, const void* res, int64_t ldr, int relu, uint32_t drop_thresh,
+                      float drop_scale, uint64_t seed, void* y, int64_t ldy, float* mean, float* rstd, int M, int C,
+                      fer_stream_t stream);
+/* Backward: g = dy * [pre-ReLU value > 0] * keep * drop_scale with the gate and the keep bits recomputed
+ * from x, res and the seed (no mask is stored); dbeta (+)= sum g, dgamma (+)= sum g * xhat over the rows;
+ * dx = gamma * rstd * (g - mean(g) - xhat * mean(g * xhat)) (train) or gamma * rstd * g (train == 0);
+ * dres (optional) = g, the gradient of the residual branch. dx, dres, dgamma, dbeta are each optional
+ * (at least one). mean / rstd: what the forward saved. */
+int fer_batchnorm_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* mean,
+                      const float* rstd, const float* gamma, const float* beta, const void* res, int64_t ldr,
+                      int relu, uint32_t drop_thresh, float drop_scale, uint64_t seed, int train, void* dx,
+                      int64_t lddx, void* dres, int64_t lddr, float* dgamma, float* dbeta, int accumulate, int M,
+                      int C, fer_stream_t stream);
+
+/* nn.AdaptiveAvgPool1d(1) + nn.Flatten (`latent_cnn.py:109,115,157,297,328`): y[b][c] = mean over l of
+ * x[b*L + l][c]; backward dx[b*L + l][c] = dy[b][c] / L. */
+int fer_seq_mean_fwd(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int B, int L, int C,
+                     fer_stream_t stream);
+int fer_seq_mean_bwd(int dtype, const void* dy, int64_t lddy, void* dx, int64_t lddx, int B, int L, int C,
+                     fer_stream_t stream);
+
+/* The final nn.Linear(D, C) of the classifiers (`latent_cnn.py:120,304`; C = 7 is below fer_gemm's
+ * N % 4 and fer_head_fwd has a LayerNorm built in): logits[b][c] = sum_d x[b][d] W[c][d] + bias[c], fp32
+ * out, W [C][D] and bias fp32 (bias optional). Backward: dx[b][d] = (sum_c dlogits[b][c] W[c][d]) *
+ * gate[b][d] (gate optional: the act' * keep * scale a fer_gemm FER_PRE_GATE_ epilogue wrote for x),
+ * dW[c][d] (+)= sum_b dlogits[b][c] x[b][d], dbias[c] (+)= sum_b dlogits[b][c]; each output optional,
+ * every sum a fixed-order loop (deterministic). */
+int fer_logits_fwd(int dtype, const void* x, int64_t ldx, const float* W, const float* bias, float* logits, int B,
+                   int D, int C, fer_stream_t stream);
+int fer_logits_bwd(int dtype, const void* x, int64_t ldx, const float* W, const float* dlogits, const void* gate,
+                   int64_t ldg, void* dx, int64_t lddx, float* dW, float* dbias, int accumulate, int B, int D, int C,
+                   fer_stream_t stream);
+
 /* Softmax cross-entropy with label smoothing and optional class weights, mean reduction
  * normalised by sum w[y] (nn.CrossEntropyLoss, `train_image_vit.py:262-267`). Writes the
  * scalar loss and dlogits = grad_scale * dloss/dlogits. */
