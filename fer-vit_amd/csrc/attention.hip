@@ -32,17 +32,6 @@ constexpr float LN2 = 0.6931471805599453f;
 FER_DEV int swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 FER_DEV int img_off(int r, int c) { return r * 128 + ((c ^ swz(r)) << 4); }
 
-// rows [0, 32*NB) of a [N][dh] column block (row stride ld) -> LDS image (zero padded)
-template <int NB>
-FER_DEV void load_image(char* img, const bf16* src, long ld, int N, int dh) {
-  for (int idx = threadIdx.x; idx < NB * 32 * 8; idx += blockDim.x) {
-    const int r = idx >> 3, c = idx & 7;
-    bf16x8 v = {};
-    if (r < N && c * 8 < dh) v = *(const bf16x8*)(src + (long)r * ld + c * 8);
-    *(bf16x8*)(img + img_off(r, c)) = v;
-  }
-}
-
 FER_DEV bf16x8 rd_row(const char* img, int r, int c) { return *(const bf16x8*)(img + img_off(r, c)); }
 // == rd_row(img, R + (lane & 31), 2s + (lane >> 5)) for img + R * 128 passed as `img`
 FER_DEV int row_base(int lane) { return (lane & 31) * 128 + (((lane >> 5) ^ swz(lane & 31)) << 4); }
@@ -275,15 +264,6 @@ FER_DEV void fwd_dma_unit(char* buf, const u32x4& rs, int unit, long ldq, int N,
   for (int ww = 0; ww < NB; ++ww) {
     img_dma_asm<NB>(buf, rs, (long)b * N, ldq, D + h * dh, N, dh, ww, lane);
     img_dma_asm<NB>(buf + NB * 32 * 128, rs, (long)b * N, ldq, 2 * D + h * dh, N, dh, ww, lane);
-  }
-}
-
-FER_DEV void fwd_load_q(bf16x8 (&qf)[4], const bf16* qkv, long ldq, int unit, int N, int H, int dh, int q, int hh) {
-  const int b = unit / H, h = unit - b * H;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int d0 = 16 * s + 8 * hh;
-    qf[s] = (q < N && d0 < dh) ? *(const bf16x8*)(qkv + ((long)b * N + q) * ldq + h * dh + d0) : bf16x8{};
   }
 }
 
@@ -1960,6 +1940,7 @@ extern "C" int fer_debug_attn_bwd_stamps(unsigned long long* host) {
 #endif
 
 extern "C" int64_t fer_attention_ws(int dtype, int B, int N, int H) {
+  if (check_dtype(dtype, "attention_ws: unknown dtype")) return -1;
   // fp32 path: P and dS slabs, then the stand-alone colsum pass's partials; bf16: the fused
   // bias-gradient partials [B][3*H*64]
   const int64_t cs = std::max<int64_t>(fer_colsum_ws(B * N, 3 * H * 128), (int64_t)B * 7 * 3 * H * 64 * 4);
@@ -1990,6 +1971,7 @@ static int pers_occ(Kern k, int threads) {
 }
 
 extern "C" int64_t fer_attention_saved_floats(int dtype, int B, int N, int H, int dh, uint32_t drop_thresh) {
+  if (check_dtype(dtype, "attention_saved_floats: unknown dtype")) return -1;
   const int64_t nb = (N + 31) / 32;
   const int64_t mask_words = (drop_thresh && pers_path(dtype, N, dh)) ? (int64_t)B * H * nb * nb * 32 : 0;
   return lse_floats(B, N, H) + mask_words;
@@ -1998,6 +1980,7 @@ extern "C" int64_t fer_attention_saved_floats(int dtype, int B, int N, int H, in
 extern "C" int fer_attention_fwd(int dtype, const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, float* lse,
                                  int64_t saved_floats, int B, int N, int H, int dh, float scale, uint32_t drop_thresh,
                                  float drop_scale, uint64_t seed, float* ws, int64_t ws_bytes, fer_stream_t stream) {
+  if (check_dtype(dtype, "attention_fwd: unknown dtype")) return -1;
   if (B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   if (saved_floats < fer_attention_saved_floats(dtype, B, N, H, dh, drop_thresh))
@@ -2077,6 +2060,7 @@ extern "C" int fer_attention_bwd(int dtype, const void* qkv, int64_t ld_qkv, con
                                  int64_t ld_dqkv, float* ws, int64_t ws_bytes, int B, int N, int H, int dh,
                                  float scale, uint32_t drop_thresh, float drop_scale, uint64_t seed, float* colsum,
                                  int colsum_accumulate, fer_stream_t stream) {
+  if (check_dtype(dtype, "attention_bwd: unknown dtype")) return -1;
   if (B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   if (saved_floats < fer_attention_saved_floats(dtype, B, N, H, dh, drop_thresh))

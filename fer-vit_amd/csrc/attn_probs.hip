@@ -291,8 +291,8 @@ using namespace fer;
 extern "C" int fer_attention_probs(int dtype, const void* qkv, int64_t ld_qkv, int B, int N, int H, int dh, float scale,
                                    int head_avg, int q0, int nq, float* probs, int64_t probs_floats,
                                    fer_stream_t stream) {
+  if (check_dtype(dtype, "attention_probs: unknown dtype")) return -1;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype != FER_BF16 && dtype != FER_F32) return set_error("attention_probs: dtype must be FER_BF16 or FER_F32");
   if (B < 0 || N < 1 || H < 1 || dh < 1) return set_error("attention_probs: needs B >= 0, N >= 1, H >= 1, dh >= 1");
   if (q0 < 0 || nq < 1 || (int64_t)q0 + nq > N) return set_error("attention_probs: query rows q0 .. q0+nq-1 outside [0, N)");
   if (!qkv || !probs) return set_error("attention_probs: null pointer");

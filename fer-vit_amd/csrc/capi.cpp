@@ -55,6 +55,7 @@ extern "C" const char* fer_version(void) { return "fervit-mi355x 0.1 (gfx950)"; 
 
 extern "C" int fer_gemm(const fer_gemm_desc* d, const fer_epilogue* e, fer_stream_t stream) {
   if (!d || !e) return fer::set_error("gemm: null descriptor");
+  if (fer::check_dtype(d->dtype, "gemm: unknown dtype")) return -1;
   return fer::gemm_launch(*d, *e, (hipStream_t)stream);
 }
 

@@ -48,9 +48,6 @@ enum { FER_ACT_NONE = 0, FER_ACT_GELU = 1, FER_ACT_RELU = 2, FER_ACT_MUL = 3 /* 
 // pre-activation v (the input-gradient GEMM then only multiplies by it: aux_act = FER_ACT_MUL).
 enum { FER_PRE_GATE = 16 };
 
-FER_DEV float bf2f(bf16 x) { return (float)x; }
-FER_DEV bf16 f2bf(float x) { return (bf16)x; }
-
 template <typename T> FER_DEV float to_f(T x);
 template <> FER_DEV float to_f<float>(float x) { return x; }
 template <> FER_DEV float to_f<bf16>(bf16 x) { return (float)x; }
@@ -96,24 +93,8 @@ FER_DEV float gelu_erf(float x) {
 }
 // GELU for the bf16 GEMM epilogue (VALU-bound there): erf by Abramowitz-Stegun 7.1.28,
 // 1 - (1 + a1 z + ... + a6 z^6)^-16 — one reciprocal, no exponential; |GELU error| <= 9e-7 in
-// fp32, two orders below the bf16 rounding of the stored activation.
-FER_DEV float gelu_erf_fast(float x) {
-  const float z = fabsf(x) * 0.70710678118654752f;
-  float p = fmaf(4.30638e-5f, z, 2.765672e-4f);
-  p = fmaf(p, z, 1.520143e-4f);
-  p = fmaf(p, z, 9.2705272e-3f);
-  p = fmaf(p, z, 4.22820123e-2f);
-  p = fmaf(p, z, 7.05230784e-2f);
-  p = fmaf(p, z, 1.0f);
-  p *= p;
-  p *= p;
-  p *= p;
-  p *= p;
-  const float e = 1.0f - __builtin_amdgcn_rcpf(p);  // erf(|x| / sqrt 2); rcp(inf) = 0
-  return 0.5f * x * (1.0f + copysignf(e, x));
-}
-// The same on two values with packed fp32 math (v_pk_fma_f32 / v_pk_mul_f32: two lanes' worth
-// per instruction); identical arithmetic per element, so bit-identical to gelu_erf_fast.
+// fp32, two orders below the bf16 rounding of the stored activation. On two values with packed
+// fp32 math (v_pk_fma_f32 / v_pk_mul_f32: two lanes' worth per instruction).
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 // A packed-math constant materialised where it is used: without the barrier the compiler hoists
 // every such constant into an SGPR pair for the whole kernel, and the GEMM's main loop then
@@ -174,47 +155,11 @@ FER_DEV f32x2 gelu_and_grad2(f32x2 x, f32x2& grad) {
   grad = __builtin_elementwise_fma(x * 0.39894228040143268f, e, cdf);
   return x * cdf;
 }
-// Four independent pairs stage by stage (the same per-element operations as gelu_and_grad2): a
-// dependent packed-f32 op right after its producer costs a hazard s_nop, and one pair's
-// polynomial is a chain of them; interleaving the pairs fills those slots.
-FER_DEV void gelu_and_grad8(f32x2 (&x)[4], f32x2 (&grad)[4]) {
-  f32x2 e[4], z[4], t[4], y[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x2 h = -0.5f * x[i] * x[i];
-    e[i] = f32x2{__expf(h[0]), __expf(h[1])};
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) z[i] = x[i] * 0.70710678118654752f;
-  const f32x2 ka = kpk(0.3275911f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x2 d = __builtin_elementwise_fma(ka, __builtin_elementwise_abs(z[i]), f32x2(1.0f));
-    t[i] = f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-  }
-  const f32x2 k0 = kpk(1.061405429f), k1 = kpk(-1.453152027f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) y[i] = __builtin_elementwise_fma(k0, t[i], k1);
-  const f32x2 k2 = kpk(1.421413741f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) y[i] = __builtin_elementwise_fma(y[i], t[i], k2);
-  const f32x2 k3 = kpk(-0.284496736f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) y[i] = __builtin_elementwise_fma(y[i], t[i], k3);
-  const f32x2 k4 = kpk(0.254829592f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) y[i] = __builtin_elementwise_fma(y[i], t[i], k4);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x2 r = 1.0f - y[i] * t[i] * e[i];
-    const f32x2 cdf = 0.5f * (1.0f + __builtin_elementwise_copysign(r, z[i]));
-    grad[i] = __builtin_elementwise_fma(x[i] * 0.39894228040143268f, e[i], cdf);
-    x[i] = x[i] * cdf;
-  }
-}
-// gelu_and_grad8 with an output scale s folded into its constants (the GEMM epilogue's dropout
-// scale: x <- x * cdf * s, grad <- (x * pdf + cdf) * s) and exp(-x^2/2) taken as exp2 of
-// x^2 * (-log2(e)/2): same formulas, roundings in a different order.
+// gelu_and_grad2 on P independent pairs stage by stage: a dependent packed-f32 op right after its
+// producer costs a hazard s_nop, and one pair's polynomial is a chain of them; interleaving the
+// pairs fills those slots. An output scale s is folded into the constants (the GEMM epilogue's
+// dropout scale: x <- x * cdf * s, grad <- (x * pdf + cdf) * s) and exp(-x^2/2) is taken as exp2 of
+// x^2 * (-log2(e)/2): same formulas as gelu_and_grad2, roundings in a different order.
 // hs = {s/2, s/2}, ps = {s/sqrt(2 pi), s/sqrt(2 pi)} (computed once by the caller, outside any
 // divergent branch).
 template <int P>
@@ -261,7 +206,6 @@ FER_DEV void gelu_and_grad_ps(f32x2 (&x)[P], f32x2 (&grad)[P], f32x2 hs, f32x2 p
     x[i] = x[i] * cdf;
   }
 }
-FER_DEV void gelu_and_grad8s(f32x2 (&x)[4], f32x2 (&grad)[4], f32x2 hs, f32x2 ps) { gelu_and_grad_ps<4>(x, grad, hs, ps); }
 FER_DEV float act_fwd(int act, float x) {
   return act == FER_ACT_GELU ? gelu_erf(x) : (act == FER_ACT_RELU ? fmaxf(x, 0.f) : x);
 }
@@ -355,11 +299,6 @@ FER_DEV float xhalf_sum(float v) {
 FER_DEV float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-FER_DEV float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
 

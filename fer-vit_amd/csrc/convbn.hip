@@ -408,13 +408,13 @@ using namespace fer;
 
 int fer::set_step_ptr_convbn(const uint64_t* p) { return set_step_ptr_here(p) == hipSuccess ? 0 : -1; }
 
-#define FER_DT_CHECK(name)                                                              \
-  if (dtype != FER_BF16 && dtype != FER_F32) return set_error(name ": unknown dtype"); \
-  const int V = dtype == FER_BF16 ? 8 : 4;
+// elements of a 16-byte piece
+static int piece_len(int dtype) { return dtype == FER_BF16 ? 8 : 4; }
 
 extern "C" int fer_conv1d_cols(int dtype, const void* x, int64_t ldx, void* cols, int64_t ldc, int B, int L, int C,
                                fer_stream_t stream) {
-  FER_DT_CHECK("conv1d_cols")
+  if (check_dtype(dtype, "conv1d_cols: unknown dtype")) return -1;
+  const int V = piece_len(dtype);
   if (B < 1 || L < 1 || C < 1) return set_error("conv1d_cols: B, L, C must be >= 1");
   if ((3 * C) % V) return set_error("conv1d_cols: 3*C must be a multiple of the 16-byte piece (8 bf16 / 4 fp32)");
   if (!x || ldx < C) return set_error("conv1d_cols: x is null or its row stride is below C");
@@ -422,18 +422,18 @@ extern "C" int fer_conv1d_cols(int dtype, const void* x, int64_t ldx, void* cols
   const long M = (long)B * L, n = M * (3 * C / V);
   if (too_many(n)) return set_error("conv1d_cols: too many elements for one launch");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(conv1d_cols_kernel<bf16>, dim3(blocks_for(n)), dim3(256), 0, st, (const bf16*)x, (long)ldx,
-                       (bf16*)cols, (long)ldc, L, C, M);
-  else
-    hipLaunchKernelGGL(conv1d_cols_kernel<float>, dim3(blocks_for(n)), dim3(256), 0, st, (const float*)x, (long)ldx,
-                       (float*)cols, (long)ldc, L, C, M);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(conv1d_cols_kernel<T>, dim3(blocks_for(n)), dim3(256), 0, st, (const T*)x, (long)ldx,
+                       (T*)cols, (long)ldc, L, C, M);
+  });
   return hip_check("conv1d_cols");
 }
 
 extern "C" int fer_conv1d_cols_bwd(int dtype, const void* dcols, int64_t ldd, const void* res, int64_t ldr, void* dx,
                                    int64_t lddx, int B, int L, int C, fer_stream_t stream) {
-  FER_DT_CHECK("conv1d_cols_bwd")
+  if (check_dtype(dtype, "conv1d_cols_bwd: unknown dtype")) return -1;
+  const int V = piece_len(dtype);
   if (B < 1 || L < 1 || C < 1) return set_error("conv1d_cols_bwd: B, L, C must be >= 1");
   if (C % V) return set_error("conv1d_cols_bwd: C must be a multiple of the 16-byte piece (8 bf16 / 4 fp32)");
   if (!piece_ok(dcols, ldd, 3 * C, V))
@@ -443,12 +443,11 @@ extern "C" int fer_conv1d_cols_bwd(int dtype, const void* dcols, int64_t ldd, co
   const long M = (long)B * L, n = M * (C / V);
   if (too_many(n)) return set_error("conv1d_cols_bwd: too many elements for one launch");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(conv1d_cols_bwd_kernel<bf16>, dim3(blocks_for(n)), dim3(256), 0, st, (const bf16*)dcols,
-                       (long)ldd, (const bf16*)res, (long)ldr, (bf16*)dx, (long)lddx, L, C, M);
-  else
-    hipLaunchKernelGGL(conv1d_cols_bwd_kernel<float>, dim3(blocks_for(n)), dim3(256), 0, st, (const float*)dcols,
-                       (long)ldd, (const float*)res, (long)ldr, (float*)dx, (long)lddx, L, C, M);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(conv1d_cols_bwd_kernel<T>, dim3(blocks_for(n)), dim3(256), 0, st, (const T*)dcols, (long)ldd,
+                       (const T*)res, (long)ldr, (T*)dx, (long)lddx, L, C, M);
+  });
   return hip_check("conv1d_cols_bwd");
 }
 
@@ -457,7 +456,8 @@ extern "C" int fer_batchnorm_fwd(int dtype, const void* x, int64_t ldx, const fl
                                  float momentum, float eps, const void* res, int64_t ldr, int relu,
                                  uint32_t drop_thresh, float drop_scale, uint64_t seed, void* y, int64_t ldy,
                                  float* mean, float* rstd, int M, int C, fer_stream_t stream) {
-  FER_DT_CHECK("batchnorm_fwd")
+  if (check_dtype(dtype, "batchnorm_fwd: unknown dtype")) return -1;
+  const int V = piece_len(dtype);
   if (M < 1 || C < 1) return set_error("batchnorm_fwd: M and C must be >= 1");
   if (C % V) return set_error("batchnorm_fwd: C must be a multiple of the 16-byte piece (8 bf16 / 4 fp32)");
   if (train && M < 2) return set_error("batchnorm_fwd: train mode needs more than 1 value per channel");
@@ -468,13 +468,13 @@ extern "C" int fer_batchnorm_fwd(int dtype, const void* x, int64_t ldx, const fl
   if (!(eps >= 0.f) || !(momentum >= 0.f && momentum <= 1.f)) return set_error("batchnorm_fwd: bad eps or momentum");
   if (check_drop_range(drop_thresh, (long)M * C, "batchnorm_fwd: dropout over >= 2^32 elements")) return -1;
   hipStream_t st = (hipStream_t)stream;
-#define FER_BN_FWD(T)                                                                                             \
-  hipLaunchKernelGGL(bn_fwd_kernel<T>, dim3(C / V), dim3(256), 0, st, (const T*)x, (long)ldx, gamma, beta,        \
-                     running_mean, running_var, (long long*)num_batches_tracked, train, momentum, eps,            \
-                     (const T*)res, (long)ldr, relu, drop_thresh, drop_scale, seed, (T*)y, (long)ldy, mean, rstd, \
-                     M, C);
-  if (dtype == FER_BF16) FER_BN_FWD(bf16) else FER_BN_FWD(float)
-#undef FER_BN_FWD
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(bn_fwd_kernel<T>, dim3(C / V), dim3(256), 0, st, (const T*)x, (long)ldx, gamma, beta,
+                       running_mean, running_var, (long long*)num_batches_tracked, train, momentum, eps,
+                       (const T*)res, (long)ldr, relu, drop_thresh, drop_scale, seed, (T*)y, (long)ldy, mean, rstd,
+                       M, C);
+  });
   return hip_check("batchnorm_fwd");
 }
 
@@ -483,7 +483,8 @@ extern "C" int fer_batchnorm_bwd(int dtype, const void* dy, int64_t lddy, const 
                                  const void* res, int64_t ldr, int relu, uint32_t drop_thresh, float drop_scale,
                                  uint64_t seed, int train, void* dx, int64_t lddx, void* dres, int64_t lddr,
                                  float* dgamma, float* dbeta, int accumulate, int M, int C, fer_stream_t stream) {
-  FER_DT_CHECK("batchnorm_bwd")
+  if (check_dtype(dtype, "batchnorm_bwd: unknown dtype")) return -1;
+  const int V = piece_len(dtype);
   if (M < 1 || C < 1) return set_error("batchnorm_bwd: M and C must be >= 1");
   if (C % V) return set_error("batchnorm_bwd: C must be a multiple of the 16-byte piece (8 bf16 / 4 fp32)");
   if (!mean || !rstd || !gamma || !beta) return set_error("batchnorm_bwd: mean, rstd, gamma, beta are required");
@@ -493,18 +494,19 @@ extern "C" int fer_batchnorm_bwd(int dtype, const void* dy, int64_t lddy, const 
     return set_error("batchnorm_bwd: dy, x, res, dx, dres need 16-byte aligned rows of stride >= C");
   if (check_drop_range(drop_thresh, (long)M * C, "batchnorm_bwd: dropout over >= 2^32 elements")) return -1;
   hipStream_t st = (hipStream_t)stream;
-#define FER_BN_BWD(T)                                                                                              \
-  hipLaunchKernelGGL(bn_bwd_kernel<T>, dim3(C / V), dim3(256), 0, st, (const T*)dy, (long)lddy, (const T*)x,       \
-                     (long)ldx, mean, rstd, gamma, beta, (const T*)res, (long)ldr, relu, drop_thresh, drop_scale,  \
-                     seed, train, (T*)dx, (long)lddx, (T*)dres, (long)lddr, dgamma, dbeta, accumulate, M, C);
-  if (dtype == FER_BF16) FER_BN_BWD(bf16) else FER_BN_BWD(float)
-#undef FER_BN_BWD
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(bn_bwd_kernel<T>, dim3(C / V), dim3(256), 0, st, (const T*)dy, (long)lddy, (const T*)x,
+                       (long)ldx, mean, rstd, gamma, beta, (const T*)res, (long)ldr, relu, drop_thresh, drop_scale,
+                       seed, train, (T*)dx, (long)lddx, (T*)dres, (long)lddr, dgamma, dbeta, accumulate, M, C);
+  });
   return hip_check("batchnorm_bwd");
 }
 
 extern "C" int fer_seq_mean_fwd(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int B, int L, int C,
                                 fer_stream_t stream) {
-  FER_DT_CHECK("seq_mean_fwd")
+  if (check_dtype(dtype, "seq_mean_fwd: unknown dtype")) return -1;
+  const int V = piece_len(dtype);
   if (B < 1 || L < 1 || C < 1) return set_error("seq_mean_fwd: B, L, C must be >= 1");
   if (C % V) return set_error("seq_mean_fwd: C must be a multiple of the 16-byte piece (8 bf16 / 4 fp32)");
   if (!piece_ok(x, ldx, C, V) || !piece_ok(y, ldy, C, V))
@@ -512,18 +514,18 @@ extern "C" int fer_seq_mean_fwd(int dtype, const void* x, int64_t ldx, void* y, 
   const long n = (long)B * (C / V);
   if (too_many(n)) return set_error("seq_mean_fwd: too many elements for one launch");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(seq_mean_fwd_kernel<bf16>, dim3(blocks_for(n)), dim3(256), 0, st, (const bf16*)x, (long)ldx,
-                       (bf16*)y, (long)ldy, B, L, C);
-  else
-    hipLaunchKernelGGL(seq_mean_fwd_kernel<float>, dim3(blocks_for(n)), dim3(256), 0, st, (const float*)x, (long)ldx,
-                       (float*)y, (long)ldy, B, L, C);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(seq_mean_fwd_kernel<T>, dim3(blocks_for(n)), dim3(256), 0, st, (const T*)x, (long)ldx, (T*)y,
+                       (long)ldy, B, L, C);
+  });
   return hip_check("seq_mean_fwd");
 }
 
 extern "C" int fer_seq_mean_bwd(int dtype, const void* dy, int64_t lddy, void* dx, int64_t lddx, int B, int L, int C,
                                 fer_stream_t stream) {
-  FER_DT_CHECK("seq_mean_bwd")
+  if (check_dtype(dtype, "seq_mean_bwd: unknown dtype")) return -1;
+  const int V = piece_len(dtype);
   if (B < 1 || L < 1 || C < 1) return set_error("seq_mean_bwd: B, L, C must be >= 1");
   if (C % V) return set_error("seq_mean_bwd: C must be a multiple of the 16-byte piece (8 bf16 / 4 fp32)");
   if (!piece_ok(dy, lddy, C, V) || !piece_ok(dx, lddx, C, V))
@@ -531,36 +533,34 @@ extern "C" int fer_seq_mean_bwd(int dtype, const void* dy, int64_t lddy, void* d
   const long n = (long)B * L * (C / V);
   if (too_many(n)) return set_error("seq_mean_bwd: too many elements for one launch");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(seq_mean_bwd_kernel<bf16>, dim3(blocks_for(n)), dim3(256), 0, st, (const bf16*)dy, (long)lddy,
-                       (bf16*)dx, (long)lddx, B, L, C);
-  else
-    hipLaunchKernelGGL(seq_mean_bwd_kernel<float>, dim3(blocks_for(n)), dim3(256), 0, st, (const float*)dy, (long)lddy,
-                       (float*)dx, (long)lddx, B, L, C);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(seq_mean_bwd_kernel<T>, dim3(blocks_for(n)), dim3(256), 0, st, (const T*)dy, (long)lddy,
+                       (T*)dx, (long)lddx, B, L, C);
+  });
   return hip_check("seq_mean_bwd");
 }
 
 extern "C" int fer_logits_fwd(int dtype, const void* x, int64_t ldx, const float* W, const float* bias, float* logits,
                               int B, int D, int C, fer_stream_t stream) {
-  if (dtype != FER_BF16 && dtype != FER_F32) return set_error("logits_fwd: unknown dtype");
+  if (check_dtype(dtype, "logits_fwd: unknown dtype")) return -1;
   if (B < 1 || D < 1 || C < 1) return set_error("logits_fwd: B, D, C must be >= 1");
   if (!x || ldx < D || !W || !logits) return set_error("logits_fwd: null operand or row stride below D");
   const long waves = (long)B * C;
   if (waves > 0x7FFFFFFFL * 4) return set_error("logits_fwd: too many elements for one launch");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(logits_fwd_kernel<bf16>, dim3((int)((waves + 3) / 4)), dim3(256), 0, st, (const bf16*)x,
-                       (long)ldx, W, bias, logits, B, D, C);
-  else
-    hipLaunchKernelGGL(logits_fwd_kernel<float>, dim3((int)((waves + 3) / 4)), dim3(256), 0, st, (const float*)x,
-                       (long)ldx, W, bias, logits, B, D, C);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(logits_fwd_kernel<T>, dim3((int)((waves + 3) / 4)), dim3(256), 0, st, (const T*)x, (long)ldx, W,
+                       bias, logits, B, D, C);
+  });
   return hip_check("logits_fwd");
 }
 
 extern "C" int fer_logits_bwd(int dtype, const void* x, int64_t ldx, const float* W, const float* dlogits,
                               const void* gate, int64_t ldg, void* dx, int64_t lddx, float* dW, float* dbias,
                               int accumulate, int B, int D, int C, fer_stream_t stream) {
-  if (dtype != FER_BF16 && dtype != FER_F32) return set_error("logits_bwd: unknown dtype");
+  if (check_dtype(dtype, "logits_bwd: unknown dtype")) return -1;
   if (B < 1 || D < 1 || C < 1) return set_error("logits_bwd: B, D, C must be >= 1");
   if (!dlogits || !W) return set_error("logits_bwd: dlogits and W are required");
   if (!dx && !dW && !dbias) return set_error("logits_bwd: no output requested");
@@ -569,11 +569,10 @@ extern "C" int fer_logits_bwd(int dtype, const void* x, int64_t ldx, const float
   const long n = (dx ? (long)B * D : 0) + (dW ? (long)C * D : 0) + (dbias ? C : 0);
   if (too_many(n)) return set_error("logits_bwd: too many elements for one launch");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(logits_bwd_kernel<bf16>, dim3(blocks_for(n)), dim3(256), 0, st, (const bf16*)x, (long)ldx, W,
-                       dlogits, (const bf16*)gate, (long)ldg, (bf16*)dx, (long)lddx, dW, dbias, accumulate, B, D, C);
-  else
-    hipLaunchKernelGGL(logits_bwd_kernel<float>, dim3(blocks_for(n)), dim3(256), 0, st, (const float*)x, (long)ldx, W,
-                       dlogits, (const float*)gate, (long)ldg, (float*)dx, (long)lddx, dW, dbias, accumulate, B, D, C);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(logits_bwd_kernel<T>, dim3(blocks_for(n)), dim3(256), 0, st, (const T*)x, (long)ldx, W, dlogits,
+                       (const T*)gate, (long)ldg, (T*)dx, (long)lddx, dW, dbias, accumulate, B, D, C);
+  });
   return hip_check("logits_bwd");
 }

@@ -54,4 +54,20 @@ inline int check_drop_range(uint32_t thresh, long elements, const char* what) {
   return 0;
 }
 
+// The ABI's dtype code. Every entry point that takes one starts with
+//   if (check_dtype(dtype, "<entry>: unknown dtype")) return -1;
+// (before its empty-shape returns), and launches a kernel template on the element type through
+//   with_dtype(dtype, [&](auto tag) { using T = typename decltype(tag)::type; ... k<T> ... (const T*)x ... });
+// so each launch and its argument list is written once. Branches that select a bf16-only or fp32-only
+// kernel (not an element type) stay ordinary ifs.
+inline int check_dtype(int dtype, const char* msg) {
+  return dtype == FER_BF16 || dtype == FER_F32 ? 0 : set_error(msg);
+}
+template <typename T> struct DtypeTag { typedef T type; };
+template <typename F>
+inline void with_dtype(int dtype, F&& f) {  // dtype has passed check_dtype
+  if (dtype == FER_BF16) f(DtypeTag<__bf16>{});
+  else f(DtypeTag<float>{});
+}
+
 }  // namespace fer

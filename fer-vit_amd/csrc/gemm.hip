@@ -130,10 +130,13 @@ FER_DEV void epi8_bf16(const EpiArgs& e, long m, long n, f32x4& v0, f32x4& v1, f
   }
 }
 
-// Epilogue kinds with the flags fixed at compile time (the 8-phase kernel's hot shapes): the
-// generic epi8_bf16 tests every flag per row piece, and its branches and the register shuffles
-// between them cost more issue slots than the arithmetic of the plain and residual epilogues.
-// Same operations in the same order as epi8_bf16, so the results are bit-identical.
+// The bf16 tile epilogue has two implementations:
+//   epi8_bf16          generic (EPI_GEN): every flag of EpiArgs tested at run time per row piece;
+//   epi8_k / epi8_kb   the fixed kinds below, flags fixed at compile time (the hot shapes): the
+//                      generic one's branches and the register shuffles between them cost more issue
+//                      slots than the arithmetic of the plain and residual epilogues.
+// The fixed kinds do the same operations as epi8_bf16 with the dropout scale folded into constants
+// (see epi8_k). epi_kind picks the kind for a launch.
 enum { EPI_GEN = 0, EPI_STORE = 1, EPI_GATE = 2, EPI_RES = 3, EPI_MUL = 4, EPI_RES2 = 5, EPI_MUL2 = 6, EPI_GATER = 7 };
 //   EPI_STORE: c = alpha*acc + bias                                   (qkv fwd, out-proj dgrad)
 //   EPI_GATE : c = drop(gelu(v)), pre = drop(gelu'(v)), v = alpha*acc + bias      (fc1 fwd)
@@ -144,22 +147,11 @@ enum { EPI_GEN = 0, EPI_STORE = 1, EPI_GATE = 2, EPI_RES = 3, EPI_MUL = 4, EPI_R
 // EPI_RES2 / EPI_MUL2: the same arithmetic as RES / MUL; the tile epilogue loads the row operand
 // straight into registers instead of LDS, which frees the LDS for two staging areas.
 constexpr int epi_base(int S) { return S == EPI_RES2 ? EPI_RES : (S == EPI_MUL2 ? EPI_MUL : S); }
-// Keep bits of 8 consecutive elements from an even index (4 hashes), as compares: the same
-// decisions as keep4 (u16 >= thr; the high half as h >= thr << 16) without packing them into an
-// integer and testing its bits again per element.
-FER_DEV void keep8(uint64_t seed, uint32_t idx, uint32_t thr, bool (&kp)[8]) {
-  const uint32_t thr_hi = thr << 16;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const uint32_t h = fer_hash(seed, (idx >> 1) + q);
-    kp[2 * q] = (h & 0xFFFFu) >= thr;
-    kp[2 * q + 1] = h >= thr_hi;
-  }
-}
-
-// keep8 for idx % 8 == 0 (the fixed kinds: 8-column pieces at n % 8 == 0, drop_ld % 8 == 0 checked by
-// epi_kind): the pair index p = idx / 2 is then a multiple of 4, so hash q's counter (p + q) ^ lo equals
-// (p ^ lo) ^ q -- one xor-add per hash instead of an add, a xor and an add. Same decisions as keep8.
+// Keep bits of 8 consecutive elements (4 hashes) as compares: the same decisions as keep4 (u16 >= thr;
+// the high half as h >= thr << 16) without packing them into an integer and testing its bits again per
+// element. Needs idx % 8 == 0 (the fixed kinds: 8-column pieces at n % 8 == 0, drop_ld % 8 == 0 checked
+// by epi_kind): the pair index p = idx / 2 is then a multiple of 4, so hash q's counter (p + q) ^ lo
+// equals (p ^ lo) ^ q -- one xor-add per hash instead of an add, a xor and an add.
 FER_DEV void keep8a(uint64_t seed, uint32_t idx, uint32_t thr, bool (&kp)[8]) {
   const uint32_t thr_hi = thr << 16, a = (idx >> 1) ^ (uint32_t)seed, hi = (uint32_t)(seed >> 32);
 #pragma unroll
@@ -171,60 +163,9 @@ FER_DEV void keep8a(uint64_t seed, uint32_t idx, uint32_t thr, bool (&kp)[8]) {
   }
 }
 
-template <int S0>
-FER_DEV void epi8_t(const EpiArgs& e, long m, long n, f32x4& v0, f32x4& v1, f32x4 b0, f32x4 b1, bf16x8 x,
-                    float ps, uint64_t seed) {
-  constexpr int S = epi_base(S0);
-  if constexpr (S == EPI_GEN) {
-    epi8_bf16(e, m, n, v0, v1, b0, b1, x, ps, seed);
-  } else {
-    v0 = v0 * e.alpha + b0;
-    v1 = v1 * e.alpha + b1;
-    if constexpr (S == EPI_GATE) {
-      f32x4 g0, g1;
-      f32x2 t;
-      f32x2 xs[4] = {v0.xy, v0.zw, v1.xy, v1.zw}, gs[4];
-      gelu_and_grad8(xs, gs);
-      v0.xy = xs[0]; v0.zw = xs[1]; v1.xy = xs[2]; v1.zw = xs[3];
-      g0.xy = gs[0]; g0.zw = gs[1]; g1.xy = gs[2]; g1.zw = gs[3];
-      (void)t;
-      if (e.drop_thresh) {
-        bool kp[8];
-        keep8(seed, (uint32_t)m * (uint32_t)e.drop_ld + (uint32_t)n, e.drop_thresh, kp);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v0[r] = kp[r] ? v0[r] * e.drop_scale : 0.f;
-          v1[r] = kp[4 + r] ? v1[r] * e.drop_scale : 0.f;
-          g0[r] = kp[r] ? g0[r] * e.drop_scale : 0.f;
-          g1[r] = kp[4 + r] ? g1[r] * e.drop_scale : 0.f;
-        }
-      }
-      *(bf16x8*)((bf16*)e.pre + m * e.ldp + n) = pack8(g0, g1);
-    }
-    if constexpr (S == EPI_RES) {
-      if (e.drop_thresh) {
-        bool kp[8];
-        keep8(seed, (uint32_t)m * (uint32_t)e.drop_ld + (uint32_t)n, e.drop_thresh, kp);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v0[r] = kp[r] ? v0[r] * e.drop_scale : 0.f;
-          v1[r] = kp[4 + r] ? v1[r] * e.drop_scale : 0.f;
-        }
-      }
-      v0 += lo4(x);
-      v1 += hi4(x);
-    }
-    if constexpr (S == EPI_MUL) {
-      v0 *= lo4(x);
-      v1 *= hi4(x);
-    }
-    *(bf16x8*)((bf16*)e.c + m * e.ldc + n) = pack8(v0, v1);
-  }
-}
-
 // The fixed kinds with the row addressing done by the caller (element offsets oc / op into c / pre
 // and the dropout index di, advanced by adds per row instead of a 64-bit multiply per store) and
-// the dropout scale folded into constants: GATE takes it in the GELU constants (gelu_and_grad8s),
+// the dropout scale folded into constants: GATE takes it in the GELU constants (gelu_and_grad_ps),
 // RES as acc * (alpha*s) + b*s (ab = alpha*s, b0 / b1 pre-scaled by the caller), so a dropped
 // element costs a select only.
 // Returns the output row piece; GATE / GATER also the pre-activation gate piece (`gp`). The caller
@@ -235,7 +176,7 @@ template <int S0, typename E>
 FER_DEV bf16x8 epi8_k(const E& e, uint32_t di, f32x4& v0, f32x4& v1, f32x4 b0, f32x4 b1, bf16x8 x,
                       uint64_t seed, float ab, f32x2 ghs, f32x2 gps, float dsr, bf16x8& gp) {
   constexpr int S = epi_base(S0);
-  static_assert(S != EPI_GEN, "generic epilogue goes through epi8_t");
+  static_assert(S != EPI_GEN, "generic epilogue goes through epi8_bf16");
   v0 = v0 * ab + b0;
   v1 = v1 * ab + b1;
   if constexpr (S == EPI_GATER) {  // scale folded into ab / b (relu(x) * s = relu(x * s), s > 0)
@@ -255,7 +196,7 @@ FER_DEV bf16x8 epi8_k(const E& e, uint32_t di, f32x4& v0, f32x4& v1, f32x4 b0, f
   if constexpr (S == EPI_GATE) {
     f32x4 g0, g1;
     f32x2 xs[4] = {v0.xy, v0.zw, v1.xy, v1.zw}, gs[4];
-    gelu_and_grad8s(xs, gs, ghs, gps);
+    gelu_and_grad_ps<4>(xs, gs, ghs, gps);
     v0.xy = xs[0]; v0.zw = xs[1]; v1.xy = xs[2]; v1.zw = xs[3];
     g0.xy = gs[0]; g0.zw = gs[1]; g1.xy = gs[2]; g1.zw = gs[3];
     if (e.drop_thresh) {
@@ -602,7 +543,7 @@ FER_DEV void tile_epilogue(const GemmArgs& g, const EpiArgs& e, f32x4 (&acc)[FN]
     b0 *= dsc;
     b1 *= dsc;
   }
-  const f32x2 ghs = f32x2(0.5f * dsc), gps = f32x2(0.39894228040143268f * dsc);  // GATE: gelu_and_grad8s
+  const f32x2 ghs = f32x2(0.5f * dsc), gps = f32x2(0.39894228040143268f * dsc);  // GATE: gelu_and_grad_ps
   const void* xs = e.res ? e.res : e.aux;  // the row operand brought in by DMA
   const long ldxs = e.res ? e.ldr : e.ldx;
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(xs), rc = make_rsrc(e.c), rp = make_rsrc(e.pre ? e.pre : e.c);
@@ -675,7 +616,7 @@ FER_DEV void tile_epilogue(const GemmArgs& g, const EpiArgs& e, f32x4 (&acc)[FN]
           if constexpr (epi_base(EK) == EPI_GATE || EK == EPI_GATER) *(bf16x8*)((bf16*)e.pre + op) = gp;
           *(bf16x8*)((bf16*)e.c + oc) = o;
         } else {
-          epi8_t<EK>(e, m, n, v0, v1, b0, b1, x, ps, seed);
+          epi8_bf16(e, m, n, v0, v1, b0, b1, x, ps, seed);
         }
         if constexpr (CS) {
           cs0 += v0;

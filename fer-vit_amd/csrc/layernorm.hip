@@ -395,6 +395,7 @@ int fer::set_step_ptr_layernorm(const uint64_t* p) { return set_step_ptr_here(p)
 extern "C" int fer_layernorm_fwd(int dtype, const void* x, int64_t ldx, const float* gamma, const float* beta,
                                  int gamma_rows, int row_div, void* y, int64_t ldy, float* mean, float* rstd, int M,
                                  int D, float eps, fer_stream_t stream) {
+  if (check_dtype(dtype, "layernorm_fwd: unknown dtype")) return -1;
   if (M <= 0) return 0;
   if (D % 4 || D > 1024 || ldx % 4 || ldy % 4) return set_error("layernorm_fwd: D must be a multiple of 4 and <= 1024");
   if (gamma_rows < 1) gamma_rows = 1;
@@ -421,12 +422,13 @@ extern "C" int fer_layernorm_fwd(int dtype, const void* x, int64_t ldx, const fl
       default: FER_LN_FWD8(4) break;
     }
 #undef FER_LN_FWD8
-  } else if (dtype == FER_BF16)
-    hipLaunchKernelGGL(ln_fwd_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (long)ldx, gamma,
-                       beta, gamma_rows, row_div, (bf16*)y, (long)ldy, mean, rstd, M, D, eps);
-  else
-    hipLaunchKernelGGL(ln_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (long)ldx,
-                       gamma, beta, gamma_rows, row_div, (float*)y, (long)ldy, mean, rstd, M, D, eps);
+  } else {
+    with_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(ln_fwd_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (long)ldx, gamma, beta,
+                         gamma_rows, row_div, (T*)y, (long)ldy, mean, rstd, M, D, eps);
+    });
+  }
   return hip_check("layernorm_fwd");
 }
 
@@ -438,6 +440,7 @@ extern "C" int fer_layernorm_bwd(int dtype, const void* dy, int64_t lddy, const 
                                  uint32_t drop_thresh, float drop_scale, uint64_t seed, float* dgamma, float* dbeta,
                                  float* dbias, int accumulate, float* ws, int64_t ws_bytes, int M, int D,
                                  fer_stream_t stream) {
+  if (check_dtype(dtype, "layernorm_bwd: unknown dtype")) return -1;
   if (M <= 0) return 0;
   if (D % 4 || D > 1024) return set_error("layernorm_bwd: D must be a multiple of 4 and <= 1024");
   if (dx_drop && check_drop_range(drop_thresh, (long)M * D, "layernorm_bwd: dropout over >= 2^32 elements"))
@@ -472,24 +475,20 @@ extern "C" int fer_layernorm_bwd(int dtype, const void* dy, int64_t lddy, const 
     part_reduce(ws, nblk, 3L * D, 3 * D, D, dgamma, dbeta, dbias, accumulate, nullptr, st);
     return hip_check("layernorm_bwd_reduce");
   }
-#define FER_LN_BWD(VP)                                                                                       \
-  if (dtype == FER_BF16)                                                                                     \
-    hipLaunchKernelGGL((ln_bwd_kernel<bf16, VP>), dim3(nblk), dim3(256), 0, st, (const bf16*)dy, (long)lddy,  \
-                       (const bf16*)x, (long)ldx, mean, rstd, gamma, gamma_rows, row_div, (const bf16*)res,   \
-                       (long)ldr, (bf16*)dx, (long)lddx, (bf16*)dx_drop, drop_thresh, drop_scale, seed, ws,   \
-                       (int)want, M, D);                                                                     \
-  else                                                                                                       \
-    hipLaunchKernelGGL((ln_bwd_kernel<float, VP>), dim3(nblk), dim3(256), 0, st, (const float*)dy,           \
-                       (long)lddy, (const float*)x, (long)ldx, mean, rstd, gamma, gamma_rows, row_div,       \
-                       (const float*)res, (long)ldr, (float*)dx, (long)lddx, (float*)dx_drop, drop_thresh,   \
-                       drop_scale, seed, ws, (int)want, M, D);
-  switch ((D + 255) / 256) {
-    case 1: FER_LN_BWD(1) break;
-    case 2: FER_LN_BWD(2) break;
-    case 3: FER_LN_BWD(3) break;
-    default: FER_LN_BWD(4) break;
-  }
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+#define FER_LN_BWD(VP)                                                                                               \
+  hipLaunchKernelGGL((ln_bwd_kernel<T, VP>), dim3(nblk), dim3(256), 0, st, (const T*)dy, (long)lddy, (const T*)x,    \
+                     (long)ldx, mean, rstd, gamma, gamma_rows, row_div, (const T*)res, (long)ldr, (T*)dx, (long)lddx, \
+                     (T*)dx_drop, drop_thresh, drop_scale, seed, ws, (int)want, M, D);
+    switch ((D + 255) / 256) {
+      case 1: FER_LN_BWD(1) break;
+      case 2: FER_LN_BWD(2) break;
+      case 3: FER_LN_BWD(3) break;
+      default: FER_LN_BWD(4) break;
+    }
 #undef FER_LN_BWD
+  });
   int rc = hip_check("layernorm_bwd");
   if (rc || !want) return rc;
   part_reduce(ws, nblk, 3L * D, 3 * D, D, dgamma, dbeta, dbias, accumulate, nullptr, st);

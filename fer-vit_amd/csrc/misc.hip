@@ -1082,6 +1082,7 @@ extern "C" int fer_reduce_flush(void) {
 
 extern "C" int fer_colsum(int dtype, const void* x, int64_t ldx, int M, int N, float* out, int accumulate,
                           const float* scale_ptr, float* ws, int64_t ws_bytes, fer_stream_t stream) {
+  if (check_dtype(dtype, "colsum: unknown dtype")) return -1;
   if (N <= 0) return 0;
   if (N % 4 || ldx % 4) return set_error("colsum: N and ld must be multiples of 4");
   const int nblk = colsum_nblk(M);
@@ -1090,39 +1091,39 @@ extern "C" int fer_colsum(int dtype, const void* x, int64_t ldx, int M, int N, f
   hipStream_t st = (hipStream_t)stream;
   ws = reduction_ws(ws, (size_t)fer_colsum_ws(M, N), N, st);
   dim3 grid(ceil_div(N / 4, 64), nblk);
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(colsum_part_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)x, (long)ldx, M, N, ws, rpb);
-  else
-    hipLaunchKernelGGL(colsum_part_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (long)ldx, M, N, ws, rpb);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(colsum_part_kernel<T>, grid, dim3(256), 0, st, (const T*)x, (long)ldx, M, N, ws, rpb);
+  });
   part_reduce(ws, nblk, N, N, N, out, nullptr, nullptr, accumulate, scale_ptr, st);
   return hip_check("colsum");
 }
 
 extern "C" int fer_im2col_patch(int dtype, const float* x, int B, int C, int Hh, int Ww, int P, void* cols,
                                 int64_t ldc, fer_stream_t stream) {
+  if (check_dtype(dtype, "im2col_patch: unknown dtype")) return -1;
   const long total = (long)B * (Hh / P) * (Ww / P) * C * P * P;
   if (total <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   if (P % 4 == 0 && Ww % 4 == 0 && ldc % 4 == 0 && total / 4 < 0x7FFFFFFFL && (uintptr_t)x % 16 == 0) {
-    if (dtype == FER_BF16)
-      hipLaunchKernelGGL(im2col4_kernel<bf16>, dim3(grid_for(total / 4)), dim3(256), 0, st, x, B, C, Hh, Ww, P,
-                         (bf16*)cols, (long)ldc);
-    else
-      hipLaunchKernelGGL(im2col4_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, st, x, B, C, Hh, Ww, P,
-                         (float*)cols, (long)ldc);
+    with_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(im2col4_kernel<T>, dim3(grid_for(total / 4)), dim3(256), 0, st, x, B, C, Hh, Ww, P, (T*)cols,
+                         (long)ldc);
+    });
     return hip_check("im2col_patch");
   }
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(im2col_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, st, x, B, C, Hh, Ww, P, (bf16*)cols,
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(im2col_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, x, B, C, Hh, Ww, P, (T*)cols,
                        (long)ldc);
-  else
-    hipLaunchKernelGGL(im2col_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, x, B, C, Hh, Ww, P,
-                       (float*)cols, (long)ldc);
+  });
   return hip_check("im2col_patch");
 }
 
 extern "C" int fer_tokens_fwd(int dtype, const void* emb, const float* cls, const float* pos, void* t, int B, int n,
                               int D, uint32_t drop_thresh, float drop_scale, uint64_t seed, fer_stream_t stream) {
+  if (check_dtype(dtype, "tokens_fwd: unknown dtype")) return -1;
   const long total = (long)B * (n + 1) * D;
   if (total <= 0) return 0;
   if (check_drop_range(drop_thresh, total, "tokens_fwd: dropout over >= 2^32 elements")) return -1;
@@ -1133,20 +1134,18 @@ extern "C" int fer_tokens_fwd(int dtype, const void* emb, const float* cls, cons
     return hip_check("tokens_fwd8");
   }
   if (D % 4 == 0) {
-    if (dtype == FER_BF16)
-      hipLaunchKernelGGL(tokens_fwd4_kernel<bf16>, dim3(grid_for(total / 4)), dim3(256), 0, st, (const bf16*)emb, cls,
-                         pos, (bf16*)t, B, n, D, drop_thresh, drop_scale, seed);
-    else
-      hipLaunchKernelGGL(tokens_fwd4_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, st, (const float*)emb,
-                         cls, pos, (float*)t, B, n, D, drop_thresh, drop_scale, seed);
+    with_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(tokens_fwd4_kernel<T>, dim3(grid_for(total / 4)), dim3(256), 0, st, (const T*)emb, cls, pos,
+                         (T*)t, B, n, D, drop_thresh, drop_scale, seed);
+    });
     return hip_check("tokens_fwd");
   }
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(tokens_fwd_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, st, (const bf16*)emb, cls, pos,
-                       (bf16*)t, B, n, D, drop_thresh, drop_scale, seed);
-  else
-    hipLaunchKernelGGL(tokens_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)emb, cls,
-                       pos, (float*)t, B, n, D, drop_thresh, drop_scale, seed);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(tokens_fwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)emb, cls, pos, (T*)t,
+                       B, n, D, drop_thresh, drop_scale, seed);
+  });
   return hip_check("tokens_fwd");
 }
 
@@ -1156,6 +1155,7 @@ extern "C" int64_t fer_tokens_bwd_ws(int B, int N, int D) { return (int64_t)toke
 extern "C" int fer_tokens_bwd(int dtype, const void* dt, void* demb, float* dcls, float* dpos, int accumulate, int B,
                               int n, int D, uint32_t drop_thresh, float drop_scale, uint64_t seed, float* ws,
                               int64_t ws_bytes, fer_stream_t stream) {
+  if (check_dtype(dtype, "tokens_bwd: unknown dtype")) return -1;
   const int N = n + 1;
   if (B <= 0) return 0;
   const int nch = tokens_chunks(B);
@@ -1175,20 +1175,18 @@ extern "C" int fer_tokens_bwd(int dtype, const void* dt, void* demb, float* dcls
   }
   if (D % 4 == 0) {
     dim3 grid4(ceil_div((long)N * D / 4, 256), nch);
-    if (dtype == FER_BF16)
-      hipLaunchKernelGGL(tokens_bwd4_kernel<bf16>, grid4, dim3(256), 0, st, (const bf16*)dt, (bf16*)demb, B, n, D,
-                         drop_thresh, drop_scale, seed, ws, bchunk);
-    else
-      hipLaunchKernelGGL(tokens_bwd4_kernel<float>, grid4, dim3(256), 0, st, (const float*)dt, (float*)demb, B, n,
-                         D, drop_thresh, drop_scale, seed, ws, bchunk);
+    with_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(tokens_bwd4_kernel<T>, grid4, dim3(256), 0, st, (const T*)dt, (T*)demb, B, n, D, drop_thresh,
+                         drop_scale, seed, ws, bchunk);
+    });
   } else {
     dim3 grid(ceil_div((long)N * D, 256), nch);
-    if (dtype == FER_BF16)
-      hipLaunchKernelGGL(tokens_bwd_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)dt, (bf16*)demb, B, n, D,
-                         drop_thresh, drop_scale, seed, ws, bchunk);
-    else
-      hipLaunchKernelGGL(tokens_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)dt, (float*)demb, B, n, D,
-                         drop_thresh, drop_scale, seed, ws, bchunk);
+    with_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(tokens_bwd_kernel<T>, grid, dim3(256), 0, st, (const T*)dt, (T*)demb, B, n, D, drop_thresh,
+                         drop_scale, seed, ws, bchunk);
+    });
   }
   if (dpos) part_reduce(ws, nch, (long)N * D, N * D, N * D, dpos, nullptr, nullptr, accumulate, nullptr, st);
   if (dcls) part_reduce(ws, nch, (long)N * D, D, D, dcls, nullptr, nullptr, accumulate, nullptr, st);
@@ -1198,15 +1196,15 @@ extern "C" int fer_tokens_bwd(int dtype, const void* dt, void* demb, float* dcls
 extern "C" int fer_head_fwd(int dtype, const void* t, int64_t row_stride, const float* ln_w, const float* ln_b,
                             float eps, const float* W, const float* bias, float* logits, float* stats, int B, int D,
                             int C, uint32_t drop_thresh, float drop_scale, uint64_t seed, fer_stream_t stream) {
+  if (check_dtype(dtype, "head_fwd: unknown dtype")) return -1;
   if (B <= 0) return 0;
   if (D > 1024) return set_error("head_fwd: D <= 1024");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(head_fwd_kernel<bf16>, dim3(B), dim3(256), 0, st, (const bf16*)t, (long)row_stride, ln_w, ln_b,
-                       eps, W, bias, logits, stats, D, C, drop_thresh, drop_scale, seed);
-  else
-    hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(B), dim3(256), 0, st, (const float*)t, (long)row_stride, ln_w,
-                       ln_b, eps, W, bias, logits, stats, D, C, drop_thresh, drop_scale, seed);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(head_fwd_kernel<T>, dim3(B), dim3(256), 0, st, (const T*)t, (long)row_stride, ln_w, ln_b, eps,
+                       W, bias, logits, stats, D, C, drop_thresh, drop_scale, seed);
+  });
   return hip_check("head_fwd");
 }
 
@@ -1217,33 +1215,31 @@ extern "C" int fer_head_bwd(int dtype, const void* t, int64_t row_stride, const 
                             int rows_total, int D_ld, float* dln_w, float* dln_b, float* dW, float* dbias,
                             int accumulate, int B, int D, int C, uint32_t drop_thresh, float drop_scale,
                             uint64_t seed, float* ws, int64_t ws_bytes, fer_stream_t stream) {
+  if (check_dtype(dtype, "head_bwd: unknown dtype")) return -1;
   if (B <= 0) return 0;
   if (D > 1024) return set_error("head_bwd: D <= 1024");
   if (!ws || ws_bytes < fer_head_bwd_ws(B, D, C)) return set_error("head_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (zero_rest && D % 4 == 0 && D_ld % 4 == 0) {
     const long total = (long)rows_total * D / 4;
-    if (dtype == FER_BF16)
-      hipLaunchKernelGGL(zero_rows4_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, st, (bf16*)dt, (long)rows_total,
+    with_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(zero_rows4_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, (T*)dt, (long)rows_total,
                          D_ld, D, (long)(row_stride / D_ld));
-    else
-      hipLaunchKernelGGL(zero_rows4_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (float*)dt,
-                         (long)rows_total, D_ld, D, (long)(row_stride / D_ld));
+    });
   } else if (zero_rest) {
     const long total = (long)rows_total * D;
-    if (dtype == FER_BF16)
-      hipLaunchKernelGGL(zero_rows_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, st, (bf16*)dt, (long)rows_total,
-                         D_ld, D, (long)(row_stride / D_ld));
-    else
-      hipLaunchKernelGGL(zero_rows_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (float*)dt,
-                         (long)rows_total, D_ld, D, (long)(row_stride / D_ld));
+    with_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(zero_rows_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, (T*)dt, (long)rows_total, D_ld,
+                         D, (long)(row_stride / D_ld));
+    });
   }
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(head_bwd_kernel<bf16>, dim3(B), dim3(256), 0, st, (const bf16*)t, (long)row_stride, ln_w, ln_b,
-                       W, stats, dlogits, (bf16*)dt, D, C, drop_thresh, drop_scale, seed, ws);
-  else
-    hipLaunchKernelGGL(head_bwd_kernel<float>, dim3(B), dim3(256), 0, st, (const float*)t, (long)row_stride, ln_w,
-                       ln_b, W, stats, dlogits, (float*)dt, D, C, drop_thresh, drop_scale, seed, ws);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(head_bwd_kernel<T>, dim3(B), dim3(256), 0, st, (const T*)t, (long)row_stride, ln_w, ln_b, W,
+                       stats, dlogits, (T*)dt, D, C, drop_thresh, drop_scale, seed, ws);
+  });
   const long ps = (long)C * D + C + 2 * D;
   if (dW) part_reduce(ws, B, ps, C * D, C * D, dW, nullptr, nullptr, accumulate, nullptr, st);
   if (dbias) part_reduce(ws + (long)C * D, B, ps, C, C, dbias, nullptr, nullptr, accumulate, nullptr, st);
@@ -1319,27 +1315,27 @@ extern "C" int fer_cast_bf16_f32(const void* x, float* y, int64_t n, fer_stream_
 }
 extern "C" int fer_axpy(int dtype, const void* x, const void* t, const float* scale_ptr, void* y, int64_t n,
                         fer_stream_t stream) {
+  if (check_dtype(dtype, "axpy: unknown dtype")) return -1;
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(axpy_kernel<bf16>, dim3(grid_for(n)), dim3(256), 0, st, (const bf16*)x, (const bf16*)t,
-                       scale_ptr, (bf16*)y, (long)n);
-  else
-    hipLaunchKernelGGL(axpy_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)x, (const float*)t,
-                       scale_ptr, (float*)y, (long)n);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(axpy_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, (const T*)x, (const T*)t, scale_ptr,
+                       (T*)y, (long)n);
+  });
   return hip_check("axpy");
 }
 static int dot_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 1023) / 1024, 1024)); }
 extern "C" int fer_dot(int dtype, const void* a, const void* b, int64_t n, float* out, int accumulate, float* ws,
                        int64_t ws_bytes, fer_stream_t stream) {
+  if (check_dtype(dtype, "dot: unknown dtype")) return -1;
   const int nb = dot_blocks(n);
   if (!ws || ws_bytes < nb * 4) return set_error("dot: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(dot_part_kernel<bf16>, dim3(nb), dim3(256), 0, st, (const bf16*)a, (const bf16*)b, (long)n, ws);
-  else
-    hipLaunchKernelGGL(dot_part_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)a, (const float*)b, (long)n,
-                       ws);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(dot_part_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)a, (const T*)b, (long)n, ws);
+  });
   hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, st, ws, nb, out, accumulate);
   return hip_check("dot");
 }
@@ -1352,15 +1348,15 @@ extern "C" int fer_clip_coef(const float* sumsq, float sq_scale, float max_norm,
 }
 extern "C" int fer_dropout(int dtype, const void* x, void* y, int64_t n, uint32_t drop_thresh, float drop_scale,
                            uint64_t seed, fer_stream_t stream) {
+  if (check_dtype(dtype, "dropout: unknown dtype")) return -1;
   if (n <= 0) return 0;
   if (check_drop_range(drop_thresh, n, "dropout: >= 2^32 elements")) return -1;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == FER_BF16)
-    hipLaunchKernelGGL(dropout_kernel<bf16>, dim3(grid_for(n)), dim3(256), 0, st, (const bf16*)x, (bf16*)y, (long)n,
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(dropout_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, (const T*)x, (T*)y, (long)n,
                        drop_thresh, drop_scale, seed);
-  else
-    hipLaunchKernelGGL(dropout_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)x, (float*)y,
-                       (long)n, drop_thresh, drop_scale, seed);
+  });
   return hip_check("dropout");
 }
 // ------------------------------------------------------------------ latent augmentation

@@ -531,8 +531,6 @@ class WplusFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cfg: LayerCfg, flat: FlatParams, spec, *P):
-        from ._lib import check, lib
-
         B, L, D = x.shape
         xc = x.contiguous().float()
         y = torch.empty_like(xc)
@@ -549,8 +547,6 @@ class WplusFn(torch.autograd.Function):
     @staticmethod
     @_deferred_reductions
     def backward(ctx, dy):
-        from ._lib import check, lib
-
         flat, P, spec = ctx.flat, ctx.P, ctx.spec
         xc, saved = ctx.saved
         B, L, D = xc.shape

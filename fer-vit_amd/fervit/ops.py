@@ -6,6 +6,7 @@ HIP stream. Nothing here has a CPU path.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional
 
@@ -35,6 +36,10 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def C_ref(x):
+    return ctypes.byref(x)
 
 
 def _dev(t: torch.Tensor) -> None:
@@ -71,6 +76,11 @@ def drop_args(p: float):
         return 65536, 0.0
     thr = max(1, min(65535, int(round(p * 65536.0))))
     return thr, 1.0 / (1.0 - p)
+
+
+def seed64(seed: int) -> int:
+    """A Python int seed as the ABI's uint64_t."""
+    return seed & 0xFFFFFFFFFFFFFFFF
 
 
 # ------------------------------------------------------------------ GEMM
@@ -117,7 +127,7 @@ def gemm(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, a_kc: bool = Tr
     e.res = ptr(res)
     e.ldr = N if res is None else res.stride(0)
     thr, sc = drop_args(dropout)
-    e.drop_thresh, e.drop_scale, e.seed = thr, sc, seed & 0xFFFFFFFFFFFFFFFF
+    e.drop_thresh, e.drop_scale, e.seed = thr, sc, seed64(seed)
     e.drop_ld = drop_ld if drop_ld is not None else N
     e.aux = ptr(aux)
     e.ldx = N if aux is None else aux.stride(0)
@@ -130,12 +140,6 @@ def gemm(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, a_kc: bool = Tr
     else:
         check(lib().fer_gemm(C_ref(d), C_ref(e), stream()), "gemm")
     return out
-
-
-def C_ref(x):
-    import ctypes
-
-    return ctypes.byref(x)
 
 
 def linear_fwd(x, w, b=None, out=None, **kw):
@@ -204,7 +208,7 @@ def layernorm_bwd(dy, x, mean, rstd, w, dx=None, res=None, dx_drop=None, dropout
     ws = WS.get(nb, x.device)
     check(lib().fer_layernorm_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), mean.data_ptr(),
                                   rstd.data_ptr(), w.data_ptr(), 1, 1, ptr(res), res.stride(0) if res is not None else D,
-                                  dx.data_ptr(), dx.stride(0), ptr(dx_drop), thr, sc, seed & (2**64 - 1),
+                                  dx.data_ptr(), dx.stride(0), ptr(dx_drop), thr, sc, seed64(seed),
                                   ptr(dgamma), ptr(dbeta), ptr(dbias), int(accumulate), ws.data_ptr(), ws.numel() * 4,
                                   M, D, stream()), "layernorm_bwd")
     return dx
@@ -226,7 +230,7 @@ def attention_fwd(qkv, out, saved, B, N, H, dh, dropout=0.0, seed=0):
     ws = WS.get(nb, qkv.device) if nb else None
     check(lib().fer_attention_fwd(dcode(qkv), qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0),
                                   saved.data_ptr(), saved.numel(), B, N, H, dh, 1.0 / math.sqrt(dh), thr, sc,
-                                  seed & (2**64 - 1), ptr(ws), 0 if ws is None else ws.numel() * 4, stream()),
+                                  seed64(seed), ptr(ws), 0 if ws is None else ws.numel() * 4, stream()),
           "attention_fwd")
     return out
 
@@ -242,7 +246,7 @@ def attention_bwd(qkv, out, dout, saved, dqkv, B, N, H, dh, dropout=0.0, seed=0,
                                   dout.data_ptr(), dout.stride(0), saved.data_ptr(), saved.numel(), dqkv.data_ptr(),
                                   dqkv.stride(0),
                                   ptr(ws), 0 if ws is None else ws.numel() * 4, B, N, H, dh, 1.0 / math.sqrt(dh),
-                                  thr, sc, seed & (2**64 - 1), ptr(colsum), int(colsum_accumulate), stream()),
+                                  thr, sc, seed64(seed), ptr(colsum), int(colsum_accumulate), stream()),
           "attention_bwd")
     return dqkv
 
@@ -317,7 +321,7 @@ def tokens_fwd(emb, cls, pos, B, n, D, dropout=0.0, seed=0):
     t = torch.empty(B * (n + 1), D, dtype=emb.dtype, device=emb.device)
     thr, sc = drop_args(dropout)
     check(lib().fer_tokens_fwd(dcode(emb), emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), t.data_ptr(), B, n, D, thr,
-                               sc, seed & (2**64 - 1), stream()), "tokens_fwd")
+                               sc, seed64(seed), stream()), "tokens_fwd")
     return t
 
 
@@ -326,7 +330,7 @@ def tokens_bwd(dt, B, n, D, dcls, dpos, accumulate, dropout=0.0, seed=0, want_de
     thr, sc = drop_args(dropout)
     ws = WS.get(lib().fer_tokens_bwd_ws(B, n + 1, D), dt.device)
     check(lib().fer_tokens_bwd(dcode(dt), dt.data_ptr(), ptr(demb), ptr(dcls), ptr(dpos), int(accumulate), B, n, D,
-                               thr, sc, seed & (2**64 - 1), ws.data_ptr(), ws.numel() * 4, stream()), "tokens_bwd")
+                               thr, sc, seed64(seed), ws.data_ptr(), ws.numel() * 4, stream()), "tokens_bwd")
     return demb
 
 
@@ -338,7 +342,7 @@ def head_fwd(t, N, lnw, lnb, eps, W, b, B, dropout=0.0, seed=0):
     thr, sc = drop_args(dropout)
     check(lib().fer_head_fwd(dcode(t), t.data_ptr(), N * t.stride(0), lnw.data_ptr(), lnb.data_ptr(), eps,
                              W.data_ptr(), b.data_ptr(), logits.data_ptr(), stats.data_ptr(), B, D, C, thr, sc,
-                             seed & (2**64 - 1), stream()), "head_fwd")
+                             seed64(seed), stream()), "head_fwd")
     return logits, stats
 
 
@@ -352,7 +356,7 @@ def head_bwd(t, N, lnw, lnb, W, stats, dlogits, B, grads, accumulate, dropout=0.
     check(lib().fer_head_bwd(dcode(t), t.data_ptr(), N * t.stride(0), lnw.data_ptr(), lnb.data_ptr(), W.data_ptr(),
                              stats.data_ptr(), dlogits.data_ptr(), dt.data_ptr(), 1, t.shape[0], t.stride(0),
                              ptr(g_lnw), ptr(g_lnb), ptr(g_W), ptr(g_b), int(accumulate), B, D, C, thr, sc,
-                             seed & (2**64 - 1), ws.data_ptr(), ws.numel() * 4, stream()), "head_bwd")
+                             seed64(seed), ws.data_ptr(), ws.numel() * 4, stream()), "head_bwd")
     return dt
 
 
@@ -394,7 +398,7 @@ def dot(a, b, out, accumulate=False):
 def dropout(x, p, seed):
     out = torch.empty_like(x)
     thr, sc = drop_args(p)
-    check(lib().fer_dropout(dcode(x), x.data_ptr(), out.data_ptr(), x.numel(), thr, sc, seed & (2**64 - 1), stream()),
+    check(lib().fer_dropout(dcode(x), x.data_ptr(), out.data_ptr(), x.numel(), thr, sc, seed64(seed), stream()),
           "dropout")
     return out
 
@@ -446,7 +450,7 @@ def batchnorm_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked
     check(lib().fer_batchnorm_fwd(dcode(x), x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(),
                                   ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), int(bool(train)),
                                   momentum, eps, ptr(res), Cc if res is None else res.stride(0), int(bool(relu)), thr,
-                                  sc, seed & (2**64 - 1), out.data_ptr(), out.stride(0), mean.data_ptr(),
+                                  sc, seed64(seed), out.data_ptr(), out.stride(0), mean.data_ptr(),
                                   rstd.data_ptr(), M, Cc, stream()), "batchnorm_fwd")
     return out, mean, rstd
 
@@ -462,7 +466,7 @@ def batchnorm_bwd(dy, x, mean, rstd, gamma, beta, train, res=None, relu=False, d
     thr, sc = drop_args(dropout)
     check(lib().fer_batchnorm_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), mean.data_ptr(),
                                   rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ptr(res),
-                                  Cc if res is None else res.stride(0), int(bool(relu)), thr, sc, seed & (2**64 - 1),
+                                  Cc if res is None else res.stride(0), int(bool(relu)), thr, sc, seed64(seed),
                                   int(bool(train)), ptr(dx), Cc if dx is None else dx.stride(0), ptr(dres),
                                   Cc if dres is None else dres.stride(0), ptr(dgamma), ptr(dbeta), int(accumulate),
                                   M, Cc, stream()), "batchnorm_bwd")

@@ -12,7 +12,9 @@
  *    allocator); the library never allocates or frees caller memory. Optional
  *    pointers may be NULL.
  *  - Activations are row-major [rows][cols]; `dtype` selects FER_BF16 (fast path,
- *    fp32 accumulation) or FER_F32 (exact parity path). Parameters, their
+ *    fp32 accumulation) or FER_F32 (exact parity path); any other code is an
+ *    error ("<entry>: unknown dtype"; the size queries that take a dtype then
+ *    return -1), checked before anything else. Parameters, their
  *    gradients, LayerNorm statistics and logits are always fp32.
  *  - Every call enqueues on `stream` and never synchronises the host.
  *  - Return 0 on success, a negative code on error; fer_last_error() then

@@ -41,7 +41,7 @@ DEV = "cuda"
 PAD, GUARD = 8, 8
 GELU_LIP = 1.13  # max |gelu'| = 1.129
 GELU_D2_MAX = 0.7979  # max |gelu''| = 2 phi(0)
-GELU_ABS = 9e-7  # csrc/common.h: stated for gelu_erf_fast; the A-S 7.1.26 forms stay below it
+GELU_ABS = 9e-7  # csrc/common.h: stated for gelu_erf_fast2; the A-S 7.1.26 forms stay below it
 GELU_GRAD_ABS = 1e-6  # gelu_erf_grad / gelu_and_grad*: DESIGN.md 2.2
 ACT = {"none": 0, "gelu": 1, "relu": 2, "mul": 3}
 PRE_GATE = 16

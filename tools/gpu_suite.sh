@@ -50,9 +50,6 @@ for s in $STEPS; do
       timeout -k 10 ${AB_TIMEOUT:-600} python -u tools/step_ab.py ${AB_ARGS:-} $AB > $OUT/${TAG}_step_ab.txt 2>&1 \
         || { tail -20 $OUT/${TAG}_step_ab.txt; exit 1; }
       grep -A40 "rounds x" $OUT/${TAG}_step_ab.txt ;;
-    fault)  # round-4 fault diagnosis: ONE launch of the faulting build; must stay the last step of a call
-      AMD_LOG_LEVEL=1 timeout -k 10 120 python -u tools/fault/run_fault.py > $OUT/${TAG}_fault.txt 2>&1
-      echo "fault step rc=$?"; grep -v "^:3:" $OUT/${TAG}_fault.txt | tail -20; exit 0 ;;
     htrace)  # kernel + HIP API trace of a short bench run: compute-queue gaps vs host API calls
       timeout -k 10 300 rocprofv3 --kernel-trace --hip-trace --output-format csv -d /tmp/${TAG}_htrace -o run -- \
         python3 bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-traffic --probe-steps 1 > $OUT/${TAG}_htrace.json 2>&1 \

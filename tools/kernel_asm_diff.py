@@ -54,7 +54,8 @@ def demangle(syms):
 
 def key(dem, drops):
     """(kernel name, template arguments) of a demangled kernel; the kernels here take ints and bools only."""
-    m = re.match(r"(?:void )?([\w:]+)(?:<([^<>]*)>)?\(", dem)
+    # (a kernel in an unnamed namespace demangles with "(anonymous namespace)::" in its qualified name)
+    m = re.match(r"(?:void )?([\w:]+)(?:<([^<>]*)>)?\(", dem.replace("(anonymous namespace)::", ""))
     if not m:  # a symbol the demangler does not know (bf16 template arguments): matched by its mangled name
         return dem, ()
     name = m.group(1).split("::")[-1]
