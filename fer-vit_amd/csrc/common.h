@@ -302,6 +302,58 @@ FER_DEV float wave_sum(float v) {
   return v;
 }
 
+// ---------------------------------------------------------------- 16-byte pieces
+// The row operators of convbn.hip and attnpool.hip move [rows][C] operands in 16-byte pieces:
+// 8 bf16 or 4 fp32 columns, converted to fp32 registers on load.
+template <typename T> struct Pc;
+template <> struct Pc<float> {
+  static constexpr int V = 4;
+  typedef f32x4 vec;
+};
+template <> struct Pc<bf16> {
+  static constexpr int V = 8;
+  typedef bf16x8 vec;
+};
+FER_DEV void loadp(const float* p, float (&v)[4]) {
+  const f32x4 t = *(const f32x4*)p;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = t[i];
+}
+FER_DEV void loadp(const bf16* p, float (&v)[8]) {
+  const bf16x8 t = *(const bf16x8*)p;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = (float)t[i];
+}
+FER_DEV void storep(float* p, const float (&v)[4]) { *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]}; }
+FER_DEV void storep(bf16* p, const float (&v)[8]) {
+  *(bf16x8*)p = bf16x8{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
+}
+
+// Sum of s[i] over the 256 threads of the workgroup, the same bits in every thread: xor butterflies
+// inside each wave (both partners add the same two values), then the four waves in a fixed order.
+template <int V>
+FER_DEV void block_sum(float (&s)[V], float (*red)[V]) {
+#pragma unroll
+  for (int i = 0; i < V; ++i) s[i] = wave_sum(s[i]);
+  __syncthreads();  // red may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) red[threadIdx.x >> 6][i] = s[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < V; ++i) s[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+}
+
+// Keep bits of the V elements of a piece starting at (even) linear index idx.
+template <int V>
+FER_DEV uint32_t keep_piece(uint64_t seed, uint32_t idx, uint32_t thr) {
+  if (!thr) return 0xFFu;
+  uint32_t k = keep4(seed, idx, thr);
+  if (V == 8) k |= keep4(seed, idx + 4, thr) << 4;
+  return k;
+}
+
 // ---------------------------------------------------------------- buffer rsrc
 // Raw buffer descriptor. Loads whose voffset >= num_records return 0: kernels
 // s_waitcnt vmcnt(N): all but this wave's N youngest vector-memory ops (loads, stores, LDS-DMA,

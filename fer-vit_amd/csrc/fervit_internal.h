@@ -31,6 +31,7 @@ int set_step_ptr_attention(const uint64_t* p);
 int set_step_ptr_layernorm(const uint64_t* p);
 int set_step_ptr_misc(const uint64_t* p);
 int set_step_ptr_convbn(const uint64_t* p);
+int set_step_ptr_attnpool(const uint64_t* p);
 int hip_check(const char* what);
 // persistent GEMM / attention kernels: walk a fixed blockIdx stride instead of the work queue
 // (fer_set_persistent_mode(1))
@@ -53,6 +54,16 @@ inline int check_drop_range(uint32_t thresh, long elements, const char* what) {
   if (thresh && elements > 0xFFFFFFFFL) return set_error(what);
   return 0;
 }
+
+// Host checks of the operators that move rows in 16-byte pieces (convbn.hip, attnpool.hip).
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// a [rows][C] operand read or written in 16-byte pieces
+inline bool piece_ok(const void* p, int64_t ld, int C, int V) { return p && al16(p) && ld >= C && ld % V == 0; }
+inline int blocks_for(long n) { return (int)((n + 255) / 256); }
+// one thread per work item, 256 per block: the block count must fit the grid's 31 bits
+inline bool too_many(long n) { return n > 0x7FFFFFFFL * 256; }
+// elements of a 16-byte piece
+inline int piece_len(int dtype) { return dtype == FER_BF16 ? 8 : 4; }
 
 // The ABI's dtype code. Every entry point that takes one starts with
 //   if (check_dtype(dtype, "<entry>: unknown dtype")) return -1;

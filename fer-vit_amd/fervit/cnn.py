@@ -14,6 +14,8 @@ modules (outside the flat store); the kernels update them in place on the device
   SeqMeanFn    AdaptiveAvgPool1d(1) + Flatten (`latent_cnn.py:157,115`)
   LogitsFn     the final Linear(D, num_classes) (`latent_cnn.py:120`)
   MlpLogitsFn  Linear -> ReLU -> Dropout -> Linear(., num_classes) (`latent_cnn.py:301-304`)
+  ProjLNFn     Linear -> LayerNorm -> ReLU -> Dropout, LatentCNNDeep's input_proj (`latent_cnn.py:183-188`)
+  AttnPoolFn   Conv1d(C, 1, 1) -> Softmax over the sequence -> weighted sum (`latent_cnn.py:207-211,256-257`)
 """
 from __future__ import annotations
 
@@ -227,3 +229,68 @@ class MlpLogitsFn(torch.autograd.Function):
         _finish(flat, P, needs)
         ctx.saved = None
         return (dx, None, None, None) + (None,) * len(P)
+
+
+class ProjLNFn(torch.autograd.Function):
+    # params: W [H,D], b [H], LayerNorm gamma [H], beta [H]
+    @staticmethod
+    def forward(ctx, x, eps: float, dropout: float, save: bool, flat: FlatParams, *P):
+        W, b, gam, beta = P
+        dt = x.dtype
+        h = ops.linear_fwd(x, _weight(flat, W, dt), None if b is None else b.data)
+        mean = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        n = ops.layernorm_fwd(h, gam.data, beta.data, eps, mean=mean, rstd=rstd)
+        seed = next_seed() if dropout > 0 else 0
+        y = ops.relu_dropout_fwd(n, dropout=dropout, seed=seed)
+        if save:
+            ctx.flat, ctx.P, ctx.dropout, ctx.seed = flat, P, dropout, seed
+            ctx.saved = (x, h, mean, rstd, n)
+        return y
+
+    @staticmethod
+    @_deferred_reductions
+    def backward(ctx, dy):
+        flat, P = ctx.flat, ctx.P
+        W, b, gam, beta = P
+        x, h, mean, rstd, n = ctx.saved
+        needs = ctx.needs_input_grad[5:]
+        G, acc = _targets(flat, P, needs)
+        gW, gb, ggam, gbeta = G
+        dn = ops.relu_dropout_bwd(dy.contiguous(), n, dropout=ctx.dropout, seed=ctx.seed)
+        dh = ops.layernorm_bwd(dn, h, mean, rstd, gam.data, dgamma=ggam, dbeta=gbeta, accumulate=acc)
+        if gb is not None:
+            ops.colsum(dh, gb, accumulate=acc)
+        if gW is not None:
+            _wgrad(dh, x, gW, accumulate=acc)
+        dx = _dgrad(flat, dh, W, dh.dtype) if ctx.needs_input_grad[0] else None
+        _finish(flat, P, needs)
+        ctx.saved = None
+        return (dx, None, None, None, None) + (None,) * len(P)
+
+
+class AttnPoolFn(torch.autograd.Function):
+    # params: attention Conv1d weight [1,C,1], bias [1] (both read as fp32 parameters)
+    @staticmethod
+    def forward(ctx, x, B: int, L: int, save: bool, flat: FlatParams, *P):
+        w, b = P
+        y, probs = ops.attnpool_fwd(x, w.data, None if b is None else b.data, B, L, want_probs=save)
+        if save:
+            ctx.flat, ctx.P, ctx.BL = flat, P, (B, L)
+            ctx.saved = (x, probs)
+        return y
+
+    @staticmethod
+    @_deferred_reductions
+    def backward(ctx, dy):
+        flat, P = ctx.flat, ctx.P
+        w, b = P
+        B, L = ctx.BL
+        x, probs = ctx.saved
+        needs = ctx.needs_input_grad[5:]
+        G, acc = _targets(flat, P, needs)
+        dx = ops.attnpool_bwd(dy.contiguous(), x, w.data, probs, B, L, dw=G[0], dbias=G[1], accumulate=acc,
+                              want_dx=ctx.needs_input_grad[0])
+        _finish(flat, P, needs)
+        ctx.saved = None
+        return (dx, None, None, None, None) + (None,) * len(P)

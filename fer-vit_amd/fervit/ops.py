@@ -518,3 +518,89 @@ def logits_bwd(x, W, dlogits, gate=None, dx=None, dW=None, dbias=None, accumulat
                                D if gate is None else gate.stride(0), ptr(dx), D if dx is None else dx.stride(0),
                                ptr(dW), ptr(dbias), int(accumulate), B, D, Cc, stream()), "logits_bwd")
     return dx
+
+
+# ------------------------------------------------------------------ LatentCNNDeep operators (csrc/attnpool.hip)
+def attnpool_fwd(x, w, bias, B, L, out=None, probs=None, want_probs=True):
+    """Attention pooling [B*L, C] -> [B, C]: softmax over each sample's L scores x w + bias, then the
+    weighted sum of its rows. w fp32 [C] (any shape with C elements), bias fp32 with one element or None.
+    Returns (y, probs): probs fp32 [B*L] for attnpool_bwd, None when want_probs is false."""
+    _rows(x, "attnpool_fwd")
+    if x.shape[0] != B * L:
+        raise ValueError("attnpool_fwd: x must have B*L rows")
+    Cc = x.shape[1]
+    if w.dtype != torch.float32 or w.numel() != Cc or not w.is_contiguous():
+        raise ValueError("attnpool_fwd: w must be a contiguous fp32 tensor of C elements")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != 1):
+        raise ValueError("attnpool_fwd: bias must be one fp32 value")
+    out = torch.empty(B, Cc, dtype=x.dtype, device=x.device) if out is None else out
+    if probs is None and want_probs:
+        probs = torch.empty(B * L, dtype=torch.float32, device=x.device)
+    check(lib().fer_attnpool_fwd(dcode(x), x.data_ptr(), x.stride(0), w.data_ptr(), ptr(bias), out.data_ptr(),
+                                 out.stride(0), ptr(probs), B, L, Cc, stream()), "attnpool_fwd")
+    return out, probs
+
+
+def attnpool_bwd(dy, x, w, probs, B, L, dx=None, dw=None, dbias=None, accumulate=False, want_dx=True):
+    """dx [B*L, C] of attnpool_fwd; dw (fp32, C elements) / dbias (fp32, one element), optional, receive
+    or accumulate the parameter gradients: the kernel writes per-sample partials, which are added over B
+    in a fixed order, dw by colsum, the single dbias column (below colsum's 4-column pieces) by dot with
+    a vector of ones."""
+    _rows(x, "attnpool_bwd")
+    _rows(dy, "attnpool_bwd")
+    if x.shape[0] != B * L or dy.shape[0] != B or dy.shape[1] != x.shape[1]:
+        raise ValueError("attnpool_bwd: x must be [B*L, C] and dy [B, C]")
+    Cc = x.shape[1]
+    if dx is None and want_dx:
+        dx = torch.empty_like(x)
+    f32 = torch.float32
+    dw_part = torch.empty(B, Cc, dtype=f32, device=x.device) if dw is not None else None
+    db_part = torch.empty(B, dtype=f32, device=x.device) if dbias is not None else None
+    if dw is not None and (dw.dtype != f32 or dw.numel() != Cc or not dw.is_contiguous()):
+        raise ValueError("attnpool_bwd: dw must be a contiguous fp32 tensor of C elements")
+    if dbias is not None and (dbias.dtype != f32 or dbias.numel() != 1):
+        raise ValueError("attnpool_bwd: dbias must be one fp32 value")
+    check(lib().fer_attnpool_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), w.data_ptr(),
+                                 probs.data_ptr(), ptr(dx), Cc if dx is None else dx.stride(0), ptr(dw_part),
+                                 ptr(db_part), B, L, Cc, stream()), "attnpool_bwd")
+    if dw is not None:
+        colsum(dw_part, dw, accumulate=accumulate)
+    if dbias is not None:
+        dot(db_part, _ones(B, x.device), dbias, accumulate=accumulate)
+    return dx
+
+
+_ONES = {}
+
+
+def _ones(n: int, device) -> torch.Tensor:
+    t = _ONES.get((device, n))
+    if t is None:
+        t = _ONES[(device, n)] = torch.ones(n, dtype=torch.float32, device=device)
+    return t
+
+
+def relu_dropout_fwd(x, dropout=0.0, seed=0, out=None):
+    """y = dropout(relu(x)) over [M, C]; the mask is a function of (seed, element index)."""
+    _rows(x, "relu_dropout_fwd")
+    M, Cc = x.shape
+    out = torch.empty_like(x) if out is None else out
+    thr, sc = drop_args(dropout)
+    check(lib().fer_relu_dropout_fwd(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, Cc, thr,
+                                     sc, seed64(seed), stream()), "relu_dropout_fwd")
+    return out
+
+
+def relu_dropout_bwd(dy, x, dropout=0.0, seed=0, out=None):
+    """dx = dy * [x > 0] * keep / (1 - p), gate and mask recomputed from the forward's x and seed."""
+    _rows(x, "relu_dropout_bwd")
+    _rows(dy, "relu_dropout_bwd")
+    if dy.shape != x.shape:
+        raise ValueError("relu_dropout_bwd: dy and x must have the same shape")
+    M, Cc = x.shape
+    out = torch.empty_like(x) if out is None else out
+    thr, sc = drop_args(dropout)
+    check(lib().fer_relu_dropout_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0),
+                                     out.data_ptr(), out.stride(0), M, Cc, thr, sc, seed64(seed), stream()),
+          "relu_dropout_bwd")
+    return out

@@ -7,15 +7,17 @@ same order so the default and custom initialisers consume the RNG identically); 
 on the HIP path (fervit/cnn.py) in token-major layout [B*L][C]. BatchNorm's running_mean,
 running_var and num_batches_tracked are ordinary module buffers, updated on the device.
 
-`create_latent_cnn('standard')` (`latent_cnn.py:66-161`, the trainer's default) and `'light'`
-(`:264-330`) are native. `'deep'` needs a softmax attention pooling and `'2d'` needs Conv2d /
-MaxPool2d / Dropout2d kernels, which the library does not have: they raise NotImplementedError.
+`create_latent_cnn('standard')` (`latent_cnn.py:66-161`, the trainer's default), `'light'`
+(`:264-330`) and `'deep'` (`:164-261`: Linear + LayerNorm projection, three conv stages with residual
+blocks, softmax attention pooling over the sequence) are native. `'2d'` needs Conv2d / MaxPool2d /
+Dropout2d kernels, which the library does not have: it raises NotImplementedError.
 """
 import torch
 import torch.nn as nn
 
 from fervit import ops
-from fervit.cnn import CnnCfg, ConvBNFn, LogitsFn, MlpLogitsFn, ResBlockFn, SeqMeanFn, bn_state
+from fervit.cnn import (AttnPoolFn, CnnCfg, ConvBNFn, LogitsFn, MlpLogitsFn, ProjLNFn, ResBlockFn, SeqMeanFn,
+                        bn_state)
 from fervit.module import FerModule
 
 
@@ -161,6 +163,93 @@ class LatentCNN(FerModule):
         return LogitsFn.apply(h, save, flat, lin2.weight, lin2.bias)
 
 
+def _check_attention(conv: nn.Conv1d, channels: int) -> None:
+    if not isinstance(conv, nn.Conv1d) or conv.in_channels != channels or conv.out_channels != 1 \
+            or conv.kernel_size != (1,) or conv.stride != (1,) or conv.padding != (0,) or conv.dilation != (1,) \
+            or conv.groups != 1:
+        raise NotImplementedError("fervit: the attention pooling has a kernel only for "
+                                  "Conv1d(C, 1, kernel_size=1, stride=1, padding=0) scores")
+
+
+class LatentCNNDeep(FerModule):
+    """Linear + LayerNorm projection to 256 -> three conv stages (256, 384, 512), each a LatentConv1D
+    and residual blocks -> softmax attention pooling over the sequence -> classifier
+    (`latent_cnn.py:164-261`)."""
+
+    def __init__(self, latent_dim: int = 512, seq_len: int = 18, num_classes: int = 7, dropout: float = 0.3):
+        super().__init__()
+        self.latent_dim = latent_dim
+        self.seq_len = seq_len
+        self.input_proj = nn.Sequential(
+            nn.Linear(latent_dim, 256),
+            nn.LayerNorm(256),
+            nn.ReLU(inplace=True),
+            nn.Dropout(dropout * 0.5),
+        )
+        self.conv_block1 = nn.Sequential(
+            LatentConv1D(256, 256, kernel_size=3, dropout=dropout),
+            LatentResBlock1D(256, kernel_size=3, dropout=dropout),
+        )
+        self.conv_block2 = nn.Sequential(
+            LatentConv1D(256, 384, kernel_size=3, dropout=dropout),
+            LatentResBlock1D(384, kernel_size=3, dropout=dropout),
+        )
+        self.conv_block3 = nn.Sequential(
+            LatentConv1D(384, 512, kernel_size=3, dropout=dropout),
+            LatentResBlock1D(512, kernel_size=3, dropout=dropout),
+            LatentResBlock1D(512, kernel_size=3, dropout=dropout),
+        )
+        self.attention = nn.Sequential(
+            nn.Conv1d(512, 1, kernel_size=1),
+            nn.Softmax(dim=2),
+        )
+        self.classifier = nn.Sequential(
+            nn.Linear(512, 512),
+            nn.BatchNorm1d(512),
+            nn.ReLU(inplace=True),
+            nn.Dropout(dropout),
+            nn.Linear(512, num_classes),
+        )
+        self._init_weights()
+
+    def _init_weights(self):
+        """`latent_cnn.py:224-235`: as the other models, plus Conv1d biases 0 and LayerNorm 1 / 0."""
+        for m in self.modules():
+            if isinstance(m, (nn.Conv1d, nn.Linear)):
+                if isinstance(m, nn.Conv1d):
+                    nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+                else:
+                    nn.init.normal_(m.weight, 0, 0.01)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            elif isinstance(m, (nn.BatchNorm1d, nn.LayerNorm)):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: (B, seq_len, latent_dim) -> logits (B, num_classes), fp32."""
+        B, L, _ = x.shape
+        flat = self.fer_flat()
+        save = self.need_grad(x, list(self.parameters()))
+        lin, ln, _, drop = self.input_proj
+        if not isinstance(ln, nn.LayerNorm) or not ln.elementwise_affine or ln.bias is None:
+            raise NotImplementedError("fervit: input_proj needs an affine LayerNorm with a bias")
+        conv = self.attention[0]
+        _check_attention(conv, self.conv_block3[0].conv.out_channels)
+        t = ProjLNFn.apply(_rows(x, self.compute_dtype()), float(ln.eps), _p(drop, self.training), save, flat,
+                           lin.weight, lin.bias, ln.weight, ln.bias)
+        for stage in (self.conv_block1, self.conv_block2, self.conv_block3):
+            for blk in stage:
+                t = blk.run_rows(t, B, L, flat, save)
+        conv = self.attention[0]
+        _check_attention(conv, t.shape[1])
+        pooled = AttnPoolFn.apply(t, B, L, save, flat, conv.weight, conv.bias)
+        lin1, bn, _, drop, lin2 = self.classifier
+        cfg = CnnCfg(B, 1, False, True, _p(drop, self.training), save)
+        h = ConvBNFn.apply(pooled, None, cfg, flat, bn_state(bn), lin1.weight, lin1.bias, bn.weight, bn.bias)
+        return LogitsFn.apply(h, save, flat, lin2.weight, lin2.bias)
+
+
 class LatentCNNLight(FerModule):
     """Three biased conv + BN + ReLU stages, mean pool, two-layer classifier (`latent_cnn.py:264-330`)."""
 
@@ -211,14 +300,13 @@ class LatentCNNLight(FerModule):
 
 def create_latent_cnn(model_type: str = "standard", latent_dim: int = 512, seq_len: int = 18, num_classes: int = 7,
                       dropout: float = 0.3):
-    """`latent_cnn.py:412-438`. 'light' and 'standard' run on the HIP path."""
+    """`latent_cnn.py:412-438`. 'light', 'standard' and 'deep' run on the HIP path."""
     if model_type == "light":
         return LatentCNNLight(latent_dim, seq_len, num_classes, dropout)
     if model_type == "standard":
         return LatentCNN(latent_dim, seq_len, num_classes, dropout=dropout, use_residual=True)
     if model_type == "deep":
-        raise NotImplementedError("create_latent_cnn('deep'): LatentCNNDeep pools with a softmax attention over the "
-                                  "sequence (Conv1d(512, 1, 1) + Softmax + weighted sum), which has no kernel here")
+        return LatentCNNDeep(latent_dim, seq_len, num_classes, dropout)
     if model_type == "2d":
         raise NotImplementedError("create_latent_cnn('2d'): LatentCNN2D needs Conv2d(3x3), MaxPool2d and Dropout2d "
                                   "kernels, which the library does not have")

@@ -310,6 +310,37 @@ int fer_logits_bwd(int dtype, const void* x, int64_t ldx, const float* W, const 
                    int64_t ldg, void* dx, int64_t lddx, float* dW, float* dbias, int accumulate, int B, int D, int C,
                    fer_stream_t stream);
 
+/* ---- LatentCNNDeep (`latent_cnn.py:164-261`), csrc/attnpool.hip. Same layout and 16-byte piece rules
+ * as the LatentCNN baseline above. */
+
+/* Attention pooling (`latent_cnn.py:207-211, 256-257`): Conv1d(C, 1, kernel_size=1) -> Softmax over the
+ * sequence -> weighted sum. x [B*L][C]; w [C] fp32 (the Conv1d weight [1][C][1] read in place, 16-byte
+ * aligned); bias one fp32 value on the device (optional).
+ *   s[b][l] = sum_c x[b*L + l][c] w[c] + bias,  a[b][.] = softmax_l(s[b][.]) (max-subtracted),
+ *   y[b][c] = sum_l a[b][l] x[b*L + l][c].
+ * y [B][C] in dtype; probs (optional, [B*L] fp32) receives a for the backward. One workgroup per sample,
+ * the L scores in LDS: L <= FER_ATTNPOOL_MAX_L, larger L is rejected. fp32 arithmetic, no atomics, no
+ * workspace; repeat calls are bit-identical. */
+#define FER_ATTNPOOL_MAX_L 4096
+int fer_attnpool_fwd(int dtype, const void* x, int64_t ldx, const float* w, const float* bias, void* y, int64_t ldy,
+                     float* probs, int B, int L, int C, fer_stream_t stream);
+/* Backward from the saved probs: da[b][l] = sum_c dy[b][c] x[b*L + l][c],
+ * ds[b][l] = a[b][l] (da[b][l] - sum_l' a[b][l'] da[b][l']), dx[b*L + l][c] = a[b][l] dy[b][c] + ds[b][l] w[c];
+ * the parameter gradients leave as per-sample partials, dw_part[b][c] = sum_l ds[b][l] x[b*L + l][c]
+ * ([B][C] fp32, 16-byte aligned) and dbias_part[b] = sum_l ds[b][l] ([B] fp32), for the caller to sum over
+ * b with fer_colsum (deterministic). dx, dw_part, dbias_part are each optional (at least one). */
+int fer_attnpool_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* w,
+                     const float* probs, void* dx, int64_t lddx, float* dw_part, float* dbias_part, int B, int L,
+                     int C, fer_stream_t stream);
+
+/* ReLU -> Dropout behind input_proj's LayerNorm (`latent_cnn.py:183-188`), element-wise over x [M][C]:
+ * y = keep * drop_scale * max(x, 0); backward dx = dy * [x > 0] * keep * drop_scale with the gate and the
+ * keep bits recomputed from x and the seed (element index r * C + c; nothing is stored). */
+int fer_relu_dropout_fwd(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int M, int C,
+                         uint32_t drop_thresh, float drop_scale, uint64_t seed, fer_stream_t stream);
+int fer_relu_dropout_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, void* dx, int64_t lddx,
+                         int M, int C, uint32_t drop_thresh, float drop_scale, uint64_t seed, fer_stream_t stream);
+
 /* Softmax cross-entropy with label smoothing and optional class weights, mean reduction
  * normalised by sum w[y] (nn.CrossEntropyLoss, `train_image_vit.py:262-267`). Writes the
  * scalar loss and dlogits = grad_scale * dloss/dlogits. */

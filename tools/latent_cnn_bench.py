@@ -1,7 +1,7 @@
-"""Times the full LatentCNN ('standard') train step of the HIP path against the identical torch.nn
+"""Times the full LatentCNN ('standard', or 'deep' with --kind deep) train step of the HIP path against the identical torch.nn
 model in eager ROCm torch on the same GPU, interleaved (DESIGN.md "LatentCNN step time").
 
-    python tools/latent_cnn_bench.py [--batches 64 256] [--dtypes bf16 fp32] [--rounds 6] [--steps 20]
+    python tools/latent_cnn_bench.py [--kind standard|deep] [--batches 64 256] [--dtypes bf16 fp32] [--rounds 6] [--steps 20]
     python tools/latent_cnn_bench.py --only native --batches 64 --dtypes bf16 --steps 30   # under a profiler
 
 Step = zero_grad, forward (dropout 0.3), CrossEntropyLoss, backward, AdamW (lr 1e-4, wd 1e-2), the
@@ -66,12 +66,33 @@ class TorchLatentCNN(nn.Module):
         return self.head(x.mean(2))
 
 
+class TorchLatentCNNDeep(nn.Module):
+    """Linear-LayerNorm-ReLU-Dropout to 256, conv + residual stages (256, 384, 512), softmax attention
+    pooling over the sequence, Linear-BN-ReLU-Dropout-Linear."""
+
+    def __init__(self, d=512, classes=7, p=0.3):
+        super().__init__()
+        self.proj = nn.Sequential(nn.Linear(d, 256), nn.LayerNorm(256), nn.ReLU(), nn.Dropout(p * 0.5))
+        self.body = nn.Sequential(ConvBlock(256, 256, p), ResBlock(256, p), ConvBlock(256, 384, p), ResBlock(384, p),
+                                  ConvBlock(384, 512, p), ResBlock(512, p), ResBlock(512, p))
+        self.attention = nn.Sequential(nn.Conv1d(512, 1, kernel_size=1), nn.Softmax(dim=2))
+        self.head = nn.Sequential(nn.Linear(512, 512), nn.BatchNorm1d(512), nn.ReLU(), nn.Dropout(p),
+                                  nn.Linear(512, classes))
+
+    def forward(self, x):
+        x = self.body(self.proj(x).transpose(1, 2))
+        return self.head(torch.sum(x * self.attention(x), dim=2))
+
+
+KIND = "standard"
+
+
 def native_step(dtype, x, y):
     from fervit.loss import CrossEntropyLoss
     from fervit.optim import FusedAdamW
     from models_fer_vit.latent_cnn import create_latent_cnn
 
-    m = create_latent_cnn("standard").cuda()
+    m = create_latent_cnn(KIND).cuda()
     m.set_precision(dtype)
     m.train()
     opt = FusedAdamW(m.parameters(), lr=1e-4, weight_decay=1e-2, model=m)
@@ -88,7 +109,7 @@ def native_step(dtype, x, y):
 
 
 def torch_step(dtype, x, y):
-    m = TorchLatentCNN().cuda()
+    m = (TorchLatentCNNDeep() if KIND == "deep" else TorchLatentCNN()).cuda()
     m.train()
     opt = torch.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=1e-2)
     crit = nn.CrossEntropyLoss()
@@ -115,13 +136,16 @@ def block(step, steps):
 
 
 def main():
+    global KIND
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", default="standard", choices=["standard", "deep"])
     ap.add_argument("--batches", type=int, nargs="+", default=[64, 256])
     ap.add_argument("--dtypes", nargs="+", default=["bf16", "fp32"], choices=["bf16", "fp32"])
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--only", choices=["native", "torch"])
     args = ap.parse_args()
+    KIND = args.kind
     if not torch.cuda.is_available():
         raise SystemExit("latent_cnn_bench: needs a ROCm device (timings on a CPU say nothing)")
     for B in args.batches:
@@ -144,7 +168,7 @@ def main():
                     ms[k].append(block(s, args.steps))
             med = {k: statistics.median(v) for k, v in ms.items()}
             for k, v in ms.items():
-                rec = {"arm": k, "model": "latent_cnn standard", "B": B, "dtype": dtype, "steps_per_block": args.steps,
+                rec = {"arm": k, "model": f"latent_cnn {KIND}", "B": B, "dtype": dtype, "steps_per_block": args.steps,
                        "blocks": len(v), "median_ms_per_step": round(med[k], 4), "min_ms_per_step": round(min(v), 4)}
                 if k == "native" and "torch" in med:
                     rec["native_over_torch"] = round(med["native"] / med["torch"], 3)
