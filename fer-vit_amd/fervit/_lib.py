@@ -96,6 +96,16 @@ SIGNATURES = {
     "fer_attnpool_bwd": (i32, [i32, vp, i64, vp, i64, fp, fp, vp, i64, fp, fp, i32, i32, i32, vp]),
     "fer_relu_dropout_fwd": (i32, [i32, vp, i64, vp, i64, i32, i32, u32, f32, u64, vp]),
     "fer_relu_dropout_bwd": (i32, [i32, vp, i64, vp, i64, vp, i64, i32, i32, u32, f32, u64, vp]),
+    "fer_grouped_linear_fwd": (i32, [i32, vp, i64, i64, vp, vp, vp, i64, i64, fp, fp, fp, i64, vp, vp, vp, i64, i64,
+                                     i32, i32, i32, i32, vp]),
+    "fer_grouped_linear_dgrad": (i32, [i32, vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, i32, i32, i32,
+                                       i32, vp]),
+    "fer_grouped_linear_wgrad": (i32, [i32, vp, vp, vp, i64, i64, vp, i64, i64, fp, fp, fp, i64, i64, fp, fp, fp, i64,
+                                       i32, u64, i32, i32, i32, i32, vp]),
+    "fer_highway_fwd": (i32, [i32, vp, vp, vp, i64, i64, fp, fp, i64, fp, fp, i64, vp, i64, i32, f32, f32, i32, vp,
+                              i64, i64, fp, fp, i32, i32, i32, vp]),
+    "fer_highway_bwd": (i32, [i32, vp, i64, i64, vp, vp, vp, i64, i64, fp, fp, fp, fp, i64, i32, i32, vp, vp, vp, i64,
+                              i64, fp, fp, i32, u64, i32, i32, i32, vp]),
     "fer_cross_entropy": (i32, [fp, vp, fp, i32, i32, f32, f32, fp, fp, vp]),
     "fer_wplus_ws": (i64, [i32, i32, i32]),
     "fer_wplus_fwd": (i32, [fp, fp, i32, i32, i32, fp, fp, vp, fp, fp, fp, fp, f32, fp, vp]),

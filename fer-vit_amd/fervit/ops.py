@@ -604,3 +604,165 @@ def relu_dropout_bwd(dy, x, dropout=0.0, seed=0, out=None):
                                      out.data_ptr(), out.stride(0), M, Cc, thr, sc, seed64(seed), stream()),
           "relu_dropout_bwd")
     return out
+
+
+# ------------------------------------------------------------------ AFS style extractor (csrc/grouped.hip)
+def _grp(t: torch.Tensor, what: str):
+    """(ld, gs) of a grouped operand [G, rows, cols]: any row / group stride, unit column stride. A
+    [B, G, K] tensor is the operand `t.transpose(0, 1)`, read or written in place."""
+    _dev(t)
+    if t.dim() != 3 or t.stride(2) != 1:
+        raise ValueError(f"{what}: [G, rows, cols] tensors with unit column stride")
+    return t.stride(1), (t.stride(0) if t.shape[0] > 1 else 0)
+
+
+def _grp_vec(t: Optional[torch.Tensor], G: int, n: int, what: str, dtype=torch.float32) -> int:
+    """Group stride of a per-group vector [G, n] (fp32 parameter, gradient or statistic)."""
+    if t is None:
+        return 0
+    _dev(t)
+    if t.dtype != dtype or t.dim() != 2 or t.shape != (G, n) or (n > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: a [G, {n}] {dtype} tensor with unit column stride")
+    return t.stride(0) if G > 1 else 0
+
+
+def _same_strides(ts, what: str):
+    st = {_grp(t, what) for t in ts}
+    if len(st) != 1 or len({t.dtype for t in ts}) != 1 or len({tuple(t.shape) for t in ts}) != 1:
+        raise ValueError(f"{what}: the sets of one launch share shape, dtype and strides")
+    return st.pop()
+
+
+def _three(ts):
+    return [ptr(ts[i]) if i < len(ts) else None for i in range(3)]
+
+
+def grouped_linear_fwd(x, ws, bs=None, outs=None):
+    """y_s[g] = x[g] w_s[g]^T + b_s[g] for 1-3 weight sets in one launch. x [G, M, K], w_s [G, N, K] (x's
+    dtype), b_s [G, N] fp32 or None, y_s [G, M, N] (allocated contiguous unless given). Returns the list y."""
+    if not 1 <= len(ws) <= 3:
+        raise ValueError("grouped_linear_fwd: one to three weight sets")
+    G, M, K = x.shape
+    N = ws[0].shape[1]
+    ldx, gsx = _grp(x, "grouped_linear_fwd")
+    ldw, gsw = _same_strides(ws, "grouped_linear_fwd")
+    if ws[0].shape != (G, N, K) or ws[0].dtype != x.dtype:
+        raise ValueError("grouped_linear_fwd: w must be [G, N, K] in x's dtype")
+    bs = [None] * len(ws) if bs is None else list(bs)
+    if len(bs) != len(ws) or len({b is None for b in bs}) != 1:
+        raise ValueError("grouped_linear_fwd: a bias for every set or for none")
+    gsb = {_grp_vec(b, G, N, "grouped_linear_fwd bias") for b in bs}
+    if len(gsb) != 1:
+        raise ValueError("grouped_linear_fwd: the biases share one group stride")
+    if outs is None:
+        outs = [torch.empty(G, M, N, dtype=x.dtype, device=x.device) for _ in ws]
+    ldy, gsy = _same_strides(outs, "grouped_linear_fwd")
+    if len(outs) != len(ws) or outs[0].shape != (G, M, N) or outs[0].dtype != x.dtype:
+        raise ValueError("grouped_linear_fwd: one [G, M, N] output per set, in x's dtype")
+    check(lib().fer_grouped_linear_fwd(dcode(x), x.data_ptr(), ldx, gsx, *_three(ws), ldw, gsw, *_three(bs),
+                                       gsb.pop(), *_three(outs), ldy, gsy, G, M, N, K, stream()),
+          "grouped_linear_fwd")
+    return outs
+
+
+def grouped_linear_dgrad(dys, ws, out=None):
+    """dx[g] = sum_s dy_s[g] w_s[g]: dy_s [G, M, N], w_s [G, N, K], dx [G, M, K]."""
+    if not 1 <= len(ws) <= 3 or len(dys) != len(ws):
+        raise ValueError("grouped_linear_dgrad: one to three weight sets, one gradient each")
+    G, M, N = dys[0].shape
+    K = ws[0].shape[2]
+    lddy, gsdy = _same_strides(dys, "grouped_linear_dgrad")
+    ldw, gsw = _same_strides(ws, "grouped_linear_dgrad")
+    if ws[0].shape != (G, N, K) or ws[0].dtype != dys[0].dtype:
+        raise ValueError("grouped_linear_dgrad: w must be [G, N, K] in dy's dtype")
+    out = torch.empty(G, M, K, dtype=dys[0].dtype, device=dys[0].device) if out is None else out
+    lddx, gsdx = _grp(out, "grouped_linear_dgrad")
+    if out.shape != (G, M, K) or out.dtype != dys[0].dtype:
+        raise ValueError("grouped_linear_dgrad: dx must be [G, M, K] in dy's dtype")
+    check(lib().fer_grouped_linear_dgrad(dcode(out), *_three(dys), lddy, gsdy, *_three(ws), ldw, gsw, out.data_ptr(),
+                                         lddx, gsdx, G, M, N, K, stream()), "grouped_linear_dgrad")
+    return out
+
+
+def grouped_linear_wgrad(dys, x, dws=None, dbs=None, accumulate=False, skip_mask=0):
+    """dw_s[g] (+)= dy_s[g]^T x[g] ([G, N, K] fp32), db_s[g] (+)= column sums of dy_s[g] ([G, N] fp32) in one
+    launch; an entry of dws / dbs may be None. skip_mask: bit g = leave group g's outputs untouched."""
+    if not 1 <= len(dys) <= 3:
+        raise ValueError("grouped_linear_wgrad: one to three gradient sets")
+    G, M, N = dys[0].shape
+    K = x.shape[2]
+    lddy, gsdy = _same_strides(dys, "grouped_linear_wgrad")
+    ldx, gsx = _grp(x, "grouped_linear_wgrad")
+    if x.shape != (G, M, K) or x.dtype != dys[0].dtype:
+        raise ValueError("grouped_linear_wgrad: x must be [G, M, K] in dy's dtype")
+    dws = [None] * len(dys) if dws is None else list(dws)
+    dbs = [None] * len(dys) if dbs is None else list(dbs)
+    if len(dws) != len(dys) or len(dbs) != len(dys):
+        raise ValueError("grouped_linear_wgrad: one dw / db entry per gradient set")
+    have = [w for w in dws if w is not None]
+    lddw, gsdw = _same_strides(have, "grouped_linear_wgrad dw") if have else (K, 0)
+    if have and (have[0].shape != (G, N, K) or have[0].dtype != torch.float32):
+        raise ValueError("grouped_linear_wgrad: dw must be [G, N, K] fp32")
+    gsdb = {_grp_vec(b, G, N, "grouped_linear_wgrad db") for b in dbs if b is not None}
+    if len(gsdb) > 1:
+        raise ValueError("grouped_linear_wgrad: the bias gradients share one group stride")
+    check(lib().fer_grouped_linear_wgrad(dcode(x), *_three(dys), lddy, gsdy, x.data_ptr(), ldx, gsx, *_three(dws),
+                                         lddw, gsdw, *_three(dbs), gsdb.pop() if gsdb else 0, int(accumulate),
+                                         int(skip_mask), G, M, N, K, stream()), "grouped_linear_wgrad")
+
+
+HIGHWAY_ACT = {"lrelu": 0, "relu": 1}
+
+
+def highway_fwd(pn, pl, pg, gamma, beta, running_mean, running_var, num_batches_tracked, train, momentum=0.1,
+                eps=1e-5, act="lrelu", out=None, want_stats=True):
+    """y = s n + (1 - s) pl, s = sigmoid(pg), n = act(BatchNorm(pn)) over [G, B, C] pre-activations; gamma, beta,
+    running_mean, running_var [G, C] fp32, num_batches_tracked [G] int64 (any group strides). train: batch
+    statistics and the running-statistic update on the device. Returns (y, mean, rstd), statistics [G, C]."""
+    G, B, Cc = pn.shape
+    ldp, gsp = _same_strides([pn, pl, pg], "highway_fwd")
+    if train and B < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {(B, Cc)}")
+    gs_par = {_grp_vec(gamma, G, Cc, "highway_fwd gamma"), _grp_vec(beta, G, Cc, "highway_fwd beta")}
+    gs_stat = {_grp_vec(running_mean, G, Cc, "highway_fwd running_mean"),
+               _grp_vec(running_var, G, Cc, "highway_fwd running_var")}
+    if len(gs_par) != 1 or len(gs_stat) != 1:
+        raise ValueError("highway_fwd: gamma / beta and running_mean / running_var share their group strides")
+    nbt = num_batches_tracked
+    gs_nbt = 0 if nbt is None else _grp_vec(nbt.view(G, 1), G, 1, "highway_fwd num_batches_tracked", torch.int64)
+    out = torch.empty(G, B, Cc, dtype=pn.dtype, device=pn.device) if out is None else out
+    ldy, gsy = _grp(out, "highway_fwd")
+    if out.shape != pn.shape or out.dtype != pn.dtype:
+        raise ValueError("highway_fwd: y must match pn")
+    mean = rstd = None
+    if want_stats:
+        mean = torch.empty(G, Cc, dtype=torch.float32, device=pn.device)
+        rstd = torch.empty_like(mean)
+    check(lib().fer_highway_fwd(dcode(pn), pn.data_ptr(), pl.data_ptr(), pg.data_ptr(), ldp, gsp, gamma.data_ptr(),
+                                beta.data_ptr(), gs_par.pop(), ptr(running_mean), ptr(running_var), gs_stat.pop(),
+                                ptr(nbt), gs_nbt, int(bool(train)), momentum, eps, HIGHWAY_ACT[act], out.data_ptr(),
+                                ldy, gsy, ptr(mean), ptr(rstd), G, B, Cc, stream()), "highway_fwd")
+    return out, mean, rstd
+
+
+def highway_bwd(dy, pn, pl, pg, mean, rstd, gamma, beta, train, act="lrelu", dgamma=None, dbeta=None,
+                accumulate=False, skip_mask=0):
+    """(dpn, dpl, dpg) of highway_fwd from dy [G, B, C] and the saved pre-activations and statistics;
+    dgamma / dbeta ([G, C] fp32 at gamma's group stride, optional) receive or accumulate."""
+    G, B, Cc = pn.shape
+    ldp, gsp = _same_strides([pn, pl, pg], "highway_bwd")
+    lddy, gsdy = _grp(dy, "highway_bwd")
+    if dy.shape != pn.shape or dy.dtype != pn.dtype:
+        raise ValueError("highway_bwd: dy must match pn")
+    gs_par = {_grp_vec(t, G, Cc, "highway_bwd parameters") for t in (gamma, beta, dgamma, dbeta) if t is not None}
+    if len(gs_par) != 1:
+        raise ValueError("highway_bwd: gamma, beta, dgamma, dbeta share one group stride")
+    if not (mean.is_contiguous() and rstd.is_contiguous() and mean.shape == (G, Cc) and rstd.shape == (G, Cc)):
+        raise ValueError("highway_bwd: mean, rstd are the contiguous [G, C] statistics of highway_fwd")
+    dp = [torch.empty(G, B, Cc, dtype=pn.dtype, device=pn.device) for _ in range(3)]
+    check(lib().fer_highway_bwd(dcode(pn), dy.data_ptr(), lddy, gsdy, pn.data_ptr(), pl.data_ptr(), pg.data_ptr(), ldp,
+                                gsp, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), gs_par.pop(),
+                                int(bool(train)), HIGHWAY_ACT[act], dp[0].data_ptr(), dp[1].data_ptr(),
+                                dp[2].data_ptr(), Cc, B * Cc if G > 1 else 0, ptr(dgamma), ptr(dbeta),
+                                int(accumulate), int(skip_mask), G, B, Cc, stream()), "highway_bwd")
+    return dp

@@ -341,6 +341,59 @@ int fer_relu_dropout_fwd(int dtype, const void* x, int64_t ldx, void* y, int64_t
 int fer_relu_dropout_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, void* dx, int64_t lddx,
                          int M, int C, uint32_t drop_thresh, float drop_scale, uint64_t seed, fer_stream_t stream);
 
+/* ---- AFS style extractor (`afs/style_extractor.py`), csrc/grouped.hip: G structurally identical blocks, one
+ * launch per stage over all of them. Every operand of group g is `base + g * group_stride` (gs*, in
+ * elements) with its own row stride (ld*), so a [B][G][K] tensor is one operand with ld = G*K, gs = K.
+ * Activations in dtype, biases and every gradient of a parameter fp32. fp32 accumulation in a fixed order,
+ * no atomics, no workspace: repeat calls are bit-identical.
+ *
+ * Shapes the kernels take (anything else is rejected with a message): K a multiple of 32, N a multiple
+ * of 16; x / w / y / dy / dx 16-byte aligned with row and group strides that are multiples of 8 elements and
+ * rows at least as long as the operand is wide; dw 16-byte aligned, strides multiples of 4; G <= 65535.
+ * Up to three weight sets share one launch (a highway layer's nonlinear / linear / gate linears read the
+ * same input): sets are given from 0 upwards, a null w1 / w2 (dy1 / dy2) ends the list. M is any count >= 1;
+ * rows beyond M are never read.
+ *
+ * forward: y_s[g] = x[g] w_s[g]^T + b_s[g], w in nn.Linear layout [N][K], x [M][K], y_s [M][N]; b_s optional.
+ * bf16: v_mfma_f32_16x16x32_bf16; fp32: FMA. */
+int fer_grouped_linear_fwd(int dtype, const void* x, int64_t ldx, int64_t gsx, const void* w0, const void* w1,
+                           const void* w2, int64_t ldw, int64_t gsw, const float* b0, const float* b1,
+                           const float* b2, int64_t gsb, void* y0, void* y1, void* y2, int64_t ldy, int64_t gsy,
+                           int G, int M, int N, int K, fer_stream_t stream);
+/* dgrad: dx[g] = sum_s dy_s[g] w_s[g]  (dy_s [M][N], dx [M][K]). */
+int fer_grouped_linear_dgrad(int dtype, const void* dy0, const void* dy1, const void* dy2, int64_t lddy, int64_t gsdy,
+                             const void* w0, const void* w1, const void* w2, int64_t ldw, int64_t gsw, void* dx,
+                             int64_t lddx, int64_t gsdx, int G, int M, int N, int K, fer_stream_t stream);
+/* wgrad: dw_s[g] (+)= dy_s[g]^T x[g] ([N][K] fp32), db_s[g] (+)= the column sums of dy_s[g] ([N] fp32), from
+ * the same launch; each dw_s / db_s is optional (at least one). accumulate: add to what the outputs hold.
+ * skip_mask: bit g set = group g's outputs are left untouched (a frozen block; G <= 64 when non-zero). */
+int fer_grouped_linear_wgrad(int dtype, const void* dy0, const void* dy1, const void* dy2, int64_t lddy, int64_t gsdy,
+                             const void* x, int64_t ldx, int64_t gsx, float* dw0, float* dw1, float* dw2,
+                             int64_t lddw, int64_t gsdw, float* db0, float* db1, float* db2, int64_t gsdb,
+                             int accumulate, uint64_t skip_mask, int G, int M, int N, int K, fer_stream_t stream);
+
+/* Highway mix (`style_extractor.py:36-40`) over pre-activations pn, pl, pg [G][B][C] (ldp, gsp):
+ *   y = s n + (1 - s) pl,  s = sigmoid(pg),  n = act(BatchNorm(pn)),  act = LeakyReLU(0.2) or ReLU,
+ * BatchNorm1d per (group, channel) over the B rows. train: biased batch variance (two-pass) for the
+ * normalisation; running_mean / running_var (fp32, gs_stat; optional) move by `momentum` towards the batch
+ * mean / UNBIASED variance and num_batches_tracked[g * gs_nbt] (optional) is advanced; B >= 2. eval: the
+ * running statistics. gamma / beta fp32 at group stride gs_par. mean / rstd (optional, [G][C] fp32)
+ * receive the statistics used, for the backward. Any C >= 1, no alignment rule. */
+enum { FER_HIGHWAY_LRELU = 0, FER_HIGHWAY_RELU = 1 };
+int fer_highway_fwd(int dtype, const void* pn, const void* pl, const void* pg, int64_t ldp, int64_t gsp,
+                    const float* gamma, const float* beta, int64_t gs_par, float* running_mean, float* running_var,
+                    int64_t gs_stat, int64_t* num_batches_tracked, int64_t gs_nbt, int train, float momentum,
+                    float eps, int act, void* y, int64_t ldy, int64_t gsy, float* mean, float* rstd, int G, int B,
+                    int C, fer_stream_t stream);
+/* Backward from dy and the forward's pn, pl, pg, mean, rstd: dpg = dy (n - pl) s (1 - s), dpl = dy (1 - s),
+ * dpn = dy s act'(.) through the BatchNorm adjoint (train: batch statistics; eval: gamma rstd only).
+ * dgamma / dbeta (fp32, group stride gs_par, optional) receive or accumulate; skip_mask as in wgrad. */
+int fer_highway_bwd(int dtype, const void* dy, int64_t lddy, int64_t gsdy, const void* pn, const void* pl,
+                    const void* pg, int64_t ldp, int64_t gsp, const float* mean, const float* rstd,
+                    const float* gamma, const float* beta, int64_t gs_par, int train, int act, void* dpn, void* dpl,
+                    void* dpg, int64_t lddp, int64_t gsdp, float* dgamma, float* dbeta, int accumulate,
+                    uint64_t skip_mask, int G, int B, int C, fer_stream_t stream);
+
 /* Softmax cross-entropy with label smoothing and optional class weights, mean reduction
  * normalised by sum w[y] (nn.CrossEntropyLoss, `train_image_vit.py:262-267`). Writes the
  * scalar loss and dlogits = grad_scale * dloss/dlogits. */
