@@ -83,6 +83,35 @@ def seed64(seed: int) -> int:
     return seed & 0xFFFFFFFFFFFFFFFF
 
 
+# The argument groups most entry points share, each as the tuple the header spells out.
+def _row(t: Optional[torch.Tensor], ld: int):
+    """(pointer, row stride) of an optional row operand; `ld` goes with a null pointer."""
+    return (None, ld) if t is None else (t.data_ptr(), t.stride(0))
+
+
+def _drop(p: float, seed: int):
+    """(drop_thresh, drop_scale, seed) of dropout probability p."""
+    return (*drop_args(p), seed64(seed))
+
+
+def _ws(nbytes: int, device, slot: int = 0, need: bool = True):
+    """(pointer, bytes) of the workspace; (null, 0) when the call needs none."""
+    if not need:
+        return None, 0
+    w = WS.get(nbytes, device, slot)
+    return w.data_ptr(), w.numel() * 4
+
+
+def _alloc(out: Optional[torch.Tensor], like: torch.Tensor, shape=None, dtype=None) -> torch.Tensor:
+    """`out` when given, else a new tensor on like's device, with like's shape and dtype unless given."""
+    if out is not None:
+        return out
+    if shape is None and dtype is None:
+        return torch.empty_like(like)
+    return torch.empty(like.shape if shape is None else shape, dtype=like.dtype if dtype is None else dtype,
+                       device=like.device)
+
+
 # ------------------------------------------------------------------ GEMM
 def gemm(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, a_kc: bool = True, b_kc: bool = True,
          M: int, N: int, K: int, lda: Optional[int] = None, ldb: Optional[int] = None, ldc: Optional[int] = None,
@@ -107,13 +136,11 @@ def gemm(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, a_kc: bool = Tr
     d.M, d.N, d.K = M, N, K
     t256 = -(-M // 256) * -(-N // 256)
     if colsum is not None:
-        w = WS.get(lib().fer_gemm_colsum_ws(M, N), A.device, slot=1)
-        d.ws, d.ws_bytes = w.data_ptr(), w.numel() * 4
+        d.ws, d.ws_bytes = _ws(lib().fer_gemm_colsum_ws(M, N), A.device, slot=1)
     elif split_ws and d.dtype == 0 and K >= 1024 and t256 < 256:
         # split-K slabs: the library targets ~one 256x256 workgroup per CU (or 512 128^2 ones)
         nb = 4 * M * N * min(32, max(2, 512 // t256)) + 4 * (-(-M // 128) * -(-N // 128)) + 256  # + tile tickets
-        w = WS.get(nb, A.device, slot=1)
-        d.ws, d.ws_bytes = w.data_ptr(), w.numel() * 4
+        d.ws, d.ws_bytes = _ws(nb, A.device, slot=1)
     e = Epilogue()
     e.c = out.data_ptr()
     e.ldc = ldc if ldc is not None else N
@@ -122,15 +149,11 @@ def gemm(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, a_kc: bool = Tr
     e.alpha = alpha
     e.bias = ptr(bias)
     e.act = ACT[act] | (PRE_GATE if pre_gate else 0)
-    e.pre = ptr(pre)
-    e.ldp = N if pre is None else pre.stride(0)
-    e.res = ptr(res)
-    e.ldr = N if res is None else res.stride(0)
-    thr, sc = drop_args(dropout)
-    e.drop_thresh, e.drop_scale, e.seed = thr, sc, seed64(seed)
+    e.pre, e.ldp = _row(pre, N)
+    e.res, e.ldr = _row(res, N)
+    e.drop_thresh, e.drop_scale, e.seed = _drop(dropout, seed)
     e.drop_ld = drop_ld if drop_ld is not None else N
-    e.aux = ptr(aux)
-    e.ldx = N if aux is None else aux.stride(0)
+    e.aux, e.ldx = _row(aux, N)
     e.aux_act = ACT[aux_act]
     e.post_scale = ptr(post_scale)
     e.colsum = ptr(colsum)
@@ -146,18 +169,14 @@ def linear_fwd(x, w, b=None, out=None, **kw):
     """y = x w^T + b for x [M,K], w [N,K] (nn.Linear)."""
     M, K = x.shape
     N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-    return gemm(x, w, out, M=M, N=N, K=K, bias=b, **kw)
+    return gemm(x, w, _alloc(out, x, (M, N)), M=M, N=N, K=K, bias=b, **kw)
 
 
 def linear_dgrad(dy, w, out=None, **kw):
     """dx = dy w for dy [M,N], w [N,K]."""
     M, N = dy.shape
     K = w.shape[1]
-    if out is None:
-        out = torch.empty(M, K, dtype=dy.dtype, device=dy.device)
-    return gemm(dy, w, out, a_kc=True, b_kc=False, M=M, N=K, K=N, lda=N, ldb=K, **kw)
+    return gemm(dy, w, _alloc(out, dy, (M, K)), a_kc=True, b_kc=False, M=M, N=K, K=N, lda=N, ldb=K, **kw)
 
 
 def linear_wgrad_group(items, splits: int = 0):
@@ -177,8 +196,8 @@ def linear_wgrad_group(items, splits: int = 0):
         arr[i] = _lib.WgradItem(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0),
                                 M, N, K, int(bool(acc)))
     nb = lib().fer_wgrad_group_ws(arr, n, splits)
-    w = WS.get(nb, items[0][0].device, slot=1) if nb > 0 else None
-    check(lib().fer_wgrad_group(arr, n, splits, ptr(w), 0 if w is None else w.numel() * 4, stream()), "wgrad_group")
+    check(lib().fer_wgrad_group(arr, n, splits, *_ws(nb, items[0][0].device, slot=1, need=nb > 0), stream()),
+          "wgrad_group")
 
 
 def linear_wgrad(dy, x, out, accumulate=False, **kw):
@@ -192,7 +211,7 @@ def linear_wgrad(dy, x, out, accumulate=False, **kw):
 # ------------------------------------------------------------------ LayerNorm
 def layernorm_fwd(x, w, b, eps, out=None, mean=None, rstd=None):
     M, D = x.shape
-    out = torch.empty_like(x) if out is None else out
+    out = _alloc(out, x)
     check(lib().fer_layernorm_fwd(dcode(x), x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(), 1, 1,
                                   out.data_ptr(), out.stride(0), ptr(mean), ptr(rstd), M, D, eps, stream()),
           "layernorm_fwd")
@@ -202,15 +221,12 @@ def layernorm_fwd(x, w, b, eps, out=None, mean=None, rstd=None):
 def layernorm_bwd(dy, x, mean, rstd, w, dx=None, res=None, dx_drop=None, dropout=0.0, seed=0, dgamma=None,
                   dbeta=None, dbias=None, accumulate=False):
     M, D = x.shape
-    dx = torch.empty_like(x) if dx is None else dx
-    thr, sc = drop_args(dropout)
-    nb = lib().fer_layernorm_bwd_ws(M, D)
-    ws = WS.get(nb, x.device)
+    dx = _alloc(dx, x)
     check(lib().fer_layernorm_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), mean.data_ptr(),
-                                  rstd.data_ptr(), w.data_ptr(), 1, 1, ptr(res), res.stride(0) if res is not None else D,
-                                  dx.data_ptr(), dx.stride(0), ptr(dx_drop), thr, sc, seed64(seed),
-                                  ptr(dgamma), ptr(dbeta), ptr(dbias), int(accumulate), ws.data_ptr(), ws.numel() * 4,
-                                  M, D, stream()), "layernorm_bwd")
+                                  rstd.data_ptr(), w.data_ptr(), 1, 1, *_row(res, D), dx.data_ptr(), dx.stride(0),
+                                  ptr(dx_drop), *_drop(dropout, seed), ptr(dgamma), ptr(dbeta), ptr(dbias),
+                                  int(accumulate), *_ws(lib().fer_layernorm_bwd_ws(M, D), x.device), M, D, stream()),
+          "layernorm_bwd")
     return dx
 
 
@@ -225,12 +241,10 @@ def attention_saved(qkv, B, N, H, dh, dropout=0.0) -> torch.Tensor:
 
 def attention_fwd(qkv, out, saved, B, N, H, dh, dropout=0.0, seed=0):
     """out = attention(qkv); `saved` from attention_saved() (same B, N, H, dh, dropout)."""
-    thr, sc = drop_args(dropout)
     nb = lib().fer_attention_ws(dcode(qkv), B, N, H)
-    ws = WS.get(nb, qkv.device) if nb else None
     check(lib().fer_attention_fwd(dcode(qkv), qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0),
-                                  saved.data_ptr(), saved.numel(), B, N, H, dh, 1.0 / math.sqrt(dh), thr, sc,
-                                  seed64(seed), ptr(ws), 0 if ws is None else ws.numel() * 4, stream()),
+                                  saved.data_ptr(), saved.numel(), B, N, H, dh, 1.0 / math.sqrt(dh),
+                                  *_drop(dropout, seed), *_ws(nb, qkv.device, need=bool(nb)), stream()),
           "attention_fwd")
     return out
 
@@ -239,15 +253,12 @@ def attention_bwd(qkv, out, dout, saved, dqkv, B, N, H, dh, dropout=0.0, seed=0,
                   colsum_accumulate=False):
     """dqkv = d(attention)/d(qkv); colsum (fp32 [3*H*dh], optional) (+)= column sums of dqkv
     (the in_proj bias gradient), fused into the backward kernel."""
-    thr, sc = drop_args(dropout)
     nb = lib().fer_attention_ws(dcode(qkv), B, N, H)
-    ws = WS.get(nb, qkv.device) if nb else None
     check(lib().fer_attention_bwd(dcode(qkv), qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0),
                                   dout.data_ptr(), dout.stride(0), saved.data_ptr(), saved.numel(), dqkv.data_ptr(),
-                                  dqkv.stride(0),
-                                  ptr(ws), 0 if ws is None else ws.numel() * 4, B, N, H, dh, 1.0 / math.sqrt(dh),
-                                  thr, sc, seed64(seed), ptr(colsum), int(colsum_accumulate), stream()),
-          "attention_bwd")
+                                  dqkv.stride(0), *_ws(nb, qkv.device, need=bool(nb)), B, N, H, dh,
+                                  1.0 / math.sqrt(dh), *_drop(dropout, seed), ptr(colsum), int(colsum_accumulate),
+                                  stream()), "attention_bwd")
     return dqkv
 
 
@@ -301,9 +312,8 @@ def attention_rollout_cls(maps, residual=0.5, out=None):
 # ------------------------------------------------------------------ misc
 def colsum(x, out, accumulate=False, scale=None):
     M, N = x.shape
-    ws = WS.get(lib().fer_colsum_ws(M, N), x.device)
     check(lib().fer_colsum(dcode(x), x.data_ptr(), x.stride(0), M, N, out.data_ptr(), int(accumulate), ptr(scale),
-                           ws.data_ptr(), ws.numel() * 4, stream()), "colsum")
+                           *_ws(lib().fer_colsum_ws(M, N), x.device), stream()), "colsum")
     return out
 
 
@@ -319,18 +329,16 @@ def im2col_patch(x, P, dtype):
 
 def tokens_fwd(emb, cls, pos, B, n, D, dropout=0.0, seed=0):
     t = torch.empty(B * (n + 1), D, dtype=emb.dtype, device=emb.device)
-    thr, sc = drop_args(dropout)
-    check(lib().fer_tokens_fwd(dcode(emb), emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), t.data_ptr(), B, n, D, thr,
-                               sc, seed64(seed), stream()), "tokens_fwd")
+    check(lib().fer_tokens_fwd(dcode(emb), emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), t.data_ptr(), B, n, D,
+                               *_drop(dropout, seed), stream()), "tokens_fwd")
     return t
 
 
 def tokens_bwd(dt, B, n, D, dcls, dpos, accumulate, dropout=0.0, seed=0, want_demb=True):
     demb = torch.empty(B * n, D, dtype=dt.dtype, device=dt.device) if want_demb else None
-    thr, sc = drop_args(dropout)
-    ws = WS.get(lib().fer_tokens_bwd_ws(B, n + 1, D), dt.device)
     check(lib().fer_tokens_bwd(dcode(dt), dt.data_ptr(), ptr(demb), ptr(dcls), ptr(dpos), int(accumulate), B, n, D,
-                               thr, sc, seed64(seed), ws.data_ptr(), ws.numel() * 4, stream()), "tokens_bwd")
+                               *_drop(dropout, seed), *_ws(lib().fer_tokens_bwd_ws(B, n + 1, D), dt.device), stream()),
+          "tokens_bwd")
     return demb
 
 
@@ -339,10 +347,9 @@ def head_fwd(t, N, lnw, lnb, eps, W, b, B, dropout=0.0, seed=0):
     C = W.shape[0]
     logits = torch.empty(B, C, dtype=torch.float32, device=t.device)
     stats = torch.empty(B, 2, dtype=torch.float32, device=t.device)
-    thr, sc = drop_args(dropout)
     check(lib().fer_head_fwd(dcode(t), t.data_ptr(), N * t.stride(0), lnw.data_ptr(), lnb.data_ptr(), eps,
-                             W.data_ptr(), b.data_ptr(), logits.data_ptr(), stats.data_ptr(), B, D, C, thr, sc,
-                             seed64(seed), stream()), "head_fwd")
+                             W.data_ptr(), b.data_ptr(), logits.data_ptr(), stats.data_ptr(), B, D, C,
+                             *_drop(dropout, seed), stream()), "head_fwd")
     return logits, stats
 
 
@@ -350,13 +357,12 @@ def head_bwd(t, N, lnw, lnb, W, stats, dlogits, B, grads, accumulate, dropout=0.
     D = t.shape[1]
     C = W.shape[0]
     dt = torch.empty_like(t)
-    thr, sc = drop_args(dropout)
-    ws = WS.get(lib().fer_head_bwd_ws(B, D, C), t.device)
     g_lnw, g_lnb, g_W, g_b = grads
     check(lib().fer_head_bwd(dcode(t), t.data_ptr(), N * t.stride(0), lnw.data_ptr(), lnb.data_ptr(), W.data_ptr(),
                              stats.data_ptr(), dlogits.data_ptr(), dt.data_ptr(), 1, t.shape[0], t.stride(0),
-                             ptr(g_lnw), ptr(g_lnb), ptr(g_W), ptr(g_b), int(accumulate), B, D, C, thr, sc,
-                             seed64(seed), ws.data_ptr(), ws.numel() * 4, stream()), "head_bwd")
+                             ptr(g_lnw), ptr(g_lnb), ptr(g_W), ptr(g_b), int(accumulate), B, D, C,
+                             *_drop(dropout, seed), *_ws(lib().fer_head_bwd_ws(B, D, C), t.device), stream()),
+          "head_bwd")
     return dt
 
 
@@ -370,36 +376,33 @@ def cross_entropy(logits, labels, weight=None, label_smoothing=0.0, grad_scale=1
 
 
 def cast_bf16(x, out=None):
-    out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if out is None else out
+    out = _alloc(out, x, dtype=torch.bfloat16)
     check(lib().fer_cast_f32_bf16(x.data_ptr(), out.data_ptr(), x.numel(), stream()), "cast")
     return out
 
 
 def cast_f32(x, out=None):
-    out = torch.empty(x.shape, dtype=torch.float32, device=x.device) if out is None else out
+    out = _alloc(out, x, dtype=torch.float32)
     check(lib().fer_cast_bf16_f32(x.data_ptr(), out.data_ptr(), x.numel(), stream()), "cast")
     return out
 
 
 def axpy(x, t, scale_ptr, out=None):
-    out = torch.empty_like(x) if out is None else out
+    out = _alloc(out, x)
     check(lib().fer_axpy(dcode(x), x.data_ptr(), t.data_ptr(), scale_ptr.data_ptr(), out.data_ptr(), x.numel(),
                          stream()), "axpy")
     return out
 
 
 def dot(a, b, out, accumulate=False):
-    ws = WS.get(4 * 1024 + 64, a.device, slot=2)
-    check(lib().fer_dot(dcode(a), a.data_ptr(), ptr(b), a.numel(), out.data_ptr(), int(accumulate), ws.data_ptr(),
-                        ws.numel() * 4, stream()), "dot")
+    check(lib().fer_dot(dcode(a), a.data_ptr(), ptr(b), a.numel(), out.data_ptr(), int(accumulate),
+                        *_ws(4 * 1024 + 64, a.device, slot=2), stream()), "dot")
     return out
 
 
 def dropout(x, p, seed):
     out = torch.empty_like(x)
-    thr, sc = drop_args(p)
-    check(lib().fer_dropout(dcode(x), x.data_ptr(), out.data_ptr(), x.numel(), thr, sc, seed64(seed), stream()),
-          "dropout")
+    check(lib().fer_dropout(dcode(x), x.data_ptr(), out.data_ptr(), x.numel(), *_drop(p, seed), stream()), "dropout")
     return out
 
 
@@ -416,7 +419,7 @@ def conv1d_cols(x, B, L, out=None):
     M, Cc = x.shape
     if M != B * L:
         raise ValueError("conv1d_cols: x must have B*L rows")
-    out = torch.empty(M, 3 * Cc, dtype=x.dtype, device=x.device) if out is None else out
+    out = _alloc(out, x, (M, 3 * Cc))
     check(lib().fer_conv1d_cols(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), B, L, Cc,
                                 stream()), "conv1d_cols")
     return out
@@ -428,10 +431,9 @@ def conv1d_cols_bwd(dcols, B, L, out=None, res=None):
     M, K = dcols.shape
     if M != B * L or K % 3:
         raise ValueError("conv1d_cols_bwd: dcols must be [B*L, 3*C]")
-    out = torch.empty(M, K // 3, dtype=dcols.dtype, device=dcols.device) if out is None else out
-    check(lib().fer_conv1d_cols_bwd(dcode(dcols), dcols.data_ptr(), dcols.stride(0), ptr(res),
-                                    K // 3 if res is None else res.stride(0), out.data_ptr(), out.stride(0),
-                                    B, L, K // 3, stream()), "conv1d_cols_bwd")
+    out = _alloc(out, dcols, (M, K // 3))
+    check(lib().fer_conv1d_cols_bwd(dcode(dcols), dcols.data_ptr(), dcols.stride(0), *_row(res, K // 3),
+                                    out.data_ptr(), out.stride(0), B, L, K // 3, stream()), "conv1d_cols_bwd")
     return out
 
 
@@ -443,15 +445,14 @@ def batchnorm_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked
     M, Cc = x.shape
     if train and M < 2:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
-    out = torch.empty_like(x) if out is None else out
-    mean = torch.empty(Cc, dtype=torch.float32, device=x.device) if mean is None else mean
-    rstd = torch.empty(Cc, dtype=torch.float32, device=x.device) if rstd is None else rstd
-    thr, sc = drop_args(dropout)
+    out = _alloc(out, x)
+    mean = _alloc(mean, x, (Cc,), torch.float32)
+    rstd = _alloc(rstd, x, (Cc,), torch.float32)
     check(lib().fer_batchnorm_fwd(dcode(x), x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(),
                                   ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), int(bool(train)),
-                                  momentum, eps, ptr(res), Cc if res is None else res.stride(0), int(bool(relu)), thr,
-                                  sc, seed64(seed), out.data_ptr(), out.stride(0), mean.data_ptr(),
-                                  rstd.data_ptr(), M, Cc, stream()), "batchnorm_fwd")
+                                  momentum, eps, *_row(res, Cc), int(bool(relu)), *_drop(dropout, seed),
+                                  out.data_ptr(), out.stride(0), mean.data_ptr(), rstd.data_ptr(), M, Cc, stream()),
+          "batchnorm_fwd")
     return out, mean, rstd
 
 
@@ -461,15 +462,11 @@ def batchnorm_bwd(dy, x, mean, rstd, gamma, beta, train, res=None, relu=False, d
     gradients. dres: pass a tensor to receive the gated gradient of the residual branch."""
     _rows(x, "batchnorm_bwd")
     M, Cc = x.shape
-    if dx is None:
-        dx = torch.empty_like(x)
-    thr, sc = drop_args(dropout)
+    dx = _alloc(dx, x)
     check(lib().fer_batchnorm_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), mean.data_ptr(),
-                                  rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ptr(res),
-                                  Cc if res is None else res.stride(0), int(bool(relu)), thr, sc, seed64(seed),
-                                  int(bool(train)), ptr(dx), Cc if dx is None else dx.stride(0), ptr(dres),
-                                  Cc if dres is None else dres.stride(0), ptr(dgamma), ptr(dbeta), int(accumulate),
-                                  M, Cc, stream()), "batchnorm_bwd")
+                                  rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), *_row(res, Cc), int(bool(relu)),
+                                  *_drop(dropout, seed), int(bool(train)), *_row(dx, Cc), *_row(dres, Cc),
+                                  ptr(dgamma), ptr(dbeta), int(accumulate), M, Cc, stream()), "batchnorm_bwd")
     return dx, dres
 
 
@@ -479,7 +476,7 @@ def seq_mean_fwd(x, B, L, out=None):
     if x.shape[0] != B * L:
         raise ValueError("seq_mean_fwd: x must have B*L rows")
     Cc = x.shape[1]
-    out = torch.empty(B, Cc, dtype=x.dtype, device=x.device) if out is None else out
+    out = _alloc(out, x, (B, Cc))
     check(lib().fer_seq_mean_fwd(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), B, L, Cc,
                                  stream()), "seq_mean_fwd")
     return out
@@ -490,7 +487,7 @@ def seq_mean_bwd(dy, B, L, out=None):
     if dy.shape[0] != B:
         raise ValueError("seq_mean_bwd: dy must have B rows")
     Cc = dy.shape[1]
-    out = torch.empty(B * L, Cc, dtype=dy.dtype, device=dy.device) if out is None else out
+    out = _alloc(out, dy, (B * L, Cc))
     check(lib().fer_seq_mean_bwd(dcode(dy), dy.data_ptr(), dy.stride(0), out.data_ptr(), out.stride(0), B, L, Cc,
                                  stream()), "seq_mean_bwd")
     return out
@@ -501,7 +498,7 @@ def logits_fwd(x, W, bias=None, out=None):
     _rows(x, "logits_fwd")
     B, D = x.shape
     Cc = W.shape[0]
-    out = torch.empty(B, Cc, dtype=torch.float32, device=x.device) if out is None else out
+    out = _alloc(out, x, (B, Cc), torch.float32)
     check(lib().fer_logits_fwd(dcode(x), x.data_ptr(), x.stride(0), W.data_ptr(), ptr(bias), out.data_ptr(), B, D, Cc,
                                stream()), "logits_fwd")
     return out
@@ -514,9 +511,8 @@ def logits_bwd(x, W, dlogits, gate=None, dx=None, dW=None, dbias=None, accumulat
     Cc = W.shape[0]
     if dx is None and want_dx:
         dx = torch.empty_like(x)
-    check(lib().fer_logits_bwd(dcode(x), x.data_ptr(), x.stride(0), W.data_ptr(), dlogits.data_ptr(), ptr(gate),
-                               D if gate is None else gate.stride(0), ptr(dx), D if dx is None else dx.stride(0),
-                               ptr(dW), ptr(dbias), int(accumulate), B, D, Cc, stream()), "logits_bwd")
+    check(lib().fer_logits_bwd(dcode(x), x.data_ptr(), x.stride(0), W.data_ptr(), dlogits.data_ptr(), *_row(gate, D),
+                               *_row(dx, D), ptr(dW), ptr(dbias), int(accumulate), B, D, Cc, stream()), "logits_bwd")
     return dx
 
 
@@ -533,7 +529,7 @@ def attnpool_fwd(x, w, bias, B, L, out=None, probs=None, want_probs=True):
         raise ValueError("attnpool_fwd: w must be a contiguous fp32 tensor of C elements")
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != 1):
         raise ValueError("attnpool_fwd: bias must be one fp32 value")
-    out = torch.empty(B, Cc, dtype=x.dtype, device=x.device) if out is None else out
+    out = _alloc(out, x, (B, Cc))
     if probs is None and want_probs:
         probs = torch.empty(B * L, dtype=torch.float32, device=x.device)
     check(lib().fer_attnpool_fwd(dcode(x), x.data_ptr(), x.stride(0), w.data_ptr(), ptr(bias), out.data_ptr(),
@@ -561,8 +557,8 @@ def attnpool_bwd(dy, x, w, probs, B, L, dx=None, dw=None, dbias=None, accumulate
     if dbias is not None and (dbias.dtype != f32 or dbias.numel() != 1):
         raise ValueError("attnpool_bwd: dbias must be one fp32 value")
     check(lib().fer_attnpool_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), w.data_ptr(),
-                                 probs.data_ptr(), ptr(dx), Cc if dx is None else dx.stride(0), ptr(dw_part),
-                                 ptr(db_part), B, L, Cc, stream()), "attnpool_bwd")
+                                 probs.data_ptr(), *_row(dx, Cc), ptr(dw_part), ptr(db_part), B, L, Cc, stream()),
+          "attnpool_bwd")
     if dw is not None:
         colsum(dw_part, dw, accumulate=accumulate)
     if dbias is not None:
@@ -584,10 +580,9 @@ def relu_dropout_fwd(x, dropout=0.0, seed=0, out=None):
     """y = dropout(relu(x)) over [M, C]; the mask is a function of (seed, element index)."""
     _rows(x, "relu_dropout_fwd")
     M, Cc = x.shape
-    out = torch.empty_like(x) if out is None else out
-    thr, sc = drop_args(dropout)
-    check(lib().fer_relu_dropout_fwd(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, Cc, thr,
-                                     sc, seed64(seed), stream()), "relu_dropout_fwd")
+    out = _alloc(out, x)
+    check(lib().fer_relu_dropout_fwd(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, Cc,
+                                     *_drop(dropout, seed), stream()), "relu_dropout_fwd")
     return out
 
 
@@ -598,10 +593,9 @@ def relu_dropout_bwd(dy, x, dropout=0.0, seed=0, out=None):
     if dy.shape != x.shape:
         raise ValueError("relu_dropout_bwd: dy and x must have the same shape")
     M, Cc = x.shape
-    out = torch.empty_like(x) if out is None else out
-    thr, sc = drop_args(dropout)
+    out = _alloc(out, x)
     check(lib().fer_relu_dropout_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0),
-                                     out.data_ptr(), out.stride(0), M, Cc, thr, sc, seed64(seed), stream()),
+                                     out.data_ptr(), out.stride(0), M, Cc, *_drop(dropout, seed), stream()),
           "relu_dropout_bwd")
     return out
 
@@ -675,7 +669,7 @@ def grouped_linear_dgrad(dys, ws, out=None):
     ldw, gsw = _same_strides(ws, "grouped_linear_dgrad")
     if ws[0].shape != (G, N, K) or ws[0].dtype != dys[0].dtype:
         raise ValueError("grouped_linear_dgrad: w must be [G, N, K] in dy's dtype")
-    out = torch.empty(G, M, K, dtype=dys[0].dtype, device=dys[0].device) if out is None else out
+    out = _alloc(out, dys[0], (G, M, K))
     lddx, gsdx = _grp(out, "grouped_linear_dgrad")
     if out.shape != (G, M, K) or out.dtype != dys[0].dtype:
         raise ValueError("grouped_linear_dgrad: dx must be [G, M, K] in dy's dtype")
@@ -730,7 +724,7 @@ def highway_fwd(pn, pl, pg, gamma, beta, running_mean, running_var, num_batches_
         raise ValueError("highway_fwd: gamma / beta and running_mean / running_var share their group strides")
     nbt = num_batches_tracked
     gs_nbt = 0 if nbt is None else _grp_vec(nbt.view(G, 1), G, 1, "highway_fwd num_batches_tracked", torch.int64)
-    out = torch.empty(G, B, Cc, dtype=pn.dtype, device=pn.device) if out is None else out
+    out = _alloc(out, pn)
     ldy, gsy = _grp(out, "highway_fwd")
     if out.shape != pn.shape or out.dtype != pn.dtype:
         raise ValueError("highway_fwd: y must match pn")

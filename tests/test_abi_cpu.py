@@ -1,6 +1,6 @@
 """CPU checks of the C ABI: the built library loads and exports every symbol that
 include/fervit.h declares (no compute calls — there is no GPU here), and the ctypes
-signature table covers exactly that set."""
+signature table and struct mirrors agree with the header's prototypes and structs, position by position."""
 import ctypes
 import os
 import re
@@ -12,10 +12,87 @@ HDR = os.path.join(ROOT, "include", "fervit.h")
 LIB = os.path.join(ROOT, "fer-vit_amd", "fervit", "libfervit.so")
 
 
+def header():
+    """include/fervit.h without its comments."""
+    return re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+
+
 def declared():
-    src = open(HDR).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(fer_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(fer_[a-z0-9_]+)\s*\(", header())))
+
+
+# ---------------------------------------------------------------------- the header, parsed
+SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64,
+           "float": ctypes.c_float, "fer_stream_t": ctypes.c_void_p}
+STRUCT_RE = r"typedef\s+struct\s*\{(.*?)\}\s*(fer_[a-z0-9_]+)\s*;"
+DECL_RE = r"(?:const\s+)?(\w+)\s*(\**)\s*(\w+)"  # [const] base [*...] name
+
+
+def header_structs():
+    """{struct name: [(field, base type, pointer depth)]} for every `typedef struct { ... } fer_*;`. A field
+    declaration that does not read as `[const] type [*] name[, name ...]` raises."""
+    out = {}
+    for body, name in re.findall(STRUCT_RE, header(), flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = (p.strip() for p in decl.split(","))
+            m = re.fullmatch(DECL_RE, first)
+            assert m and all(re.fullmatch(r"\w+", n) for n in more), f"{name}: unreadable field declaration {decl!r}"
+            fields += [(n, m.group(1), len(m.group(2))) for n in (m.group(3), *more)]
+        out[name] = fields
+    return out
+
+
+def header_prototypes():
+    """{entry point: (return (base, pointer depth), [(parameter, base, pointer depth)])}. Every statement of
+    the header that names fer_*( must read as a prototype; one that does not raises."""
+    src = re.sub(STRUCT_RE, "", header(), flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M).replace('extern "C" {', "")
+    out = {}
+    for stmt in (s.strip() for s in src.split(";")):
+        if not re.search(r"\bfer_[a-z0-9_]+\s*\(", stmt):
+            continue
+        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)\s*(fer_[a-z0-9_]+)\s*\(([^()]*)\)", stmt, flags=re.S)
+        assert m, f"unreadable prototype {stmt!r}"
+        params = []
+        if m.group(4).strip() != "void":
+            for p in m.group(4).split(","):
+                pm = re.fullmatch(DECL_RE, " ".join(p.split()))
+                assert pm, f"{m.group(3)}: unreadable parameter {p.strip()!r}"
+                params.append((pm.group(3), pm.group(1), len(pm.group(2))))
+        assert m.group(3) not in out, f"{m.group(3)} declared twice"
+        out[m.group(3)] = ((m.group(1), len(m.group(2))), params)
+    return out
+
+
+def is_pointer_type(t):
+    return isinstance(t, type) and issubclass(t, ctypes._Pointer)
+
+
+def type_mismatch(base, depth, ct, mirrors):
+    """None when ctypes type `ct` carries the C type `base` + depth stars, else what the header says."""
+    c_name = base + "*" * depth
+    if depth == 0:
+        assert base in SCALARS, f"no ctypes counterpart known for the header's {base!r}"
+        return None if ct is SCALARS[base] else c_name
+    if ct in (ctypes.c_void_p, ctypes.c_char_p):
+        return None
+    if not is_pointer_type(ct):
+        return c_name
+    # a typed pointer says what it points to: the mirror of the header's struct, or its scalar
+    pointee = (mirrors.get(base) or SCALARS.get(base)) if depth == 1 else None
+    return None if pointee is not None and ct._type_ is pointee else c_name
+
+
+def natural_layout(fields):
+    """(offsets, size) of scalar / pointer fields under natural alignment (each at a multiple of its size)."""
+    offs, off, align = [], 0, 1
+    for _, base, depth in fields:
+        n = 8 if depth else ctypes.sizeof(SCALARS[base])
+        off = -(-off // n) * n
+        offs.append(off)
+        off, align = off + n, max(align, n)
+    return offs, -(-off // align) * align
 
 
 def test_header_declares_entry_points():
@@ -35,11 +112,56 @@ def test_library_exports_every_declared_symbol():
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libfervit.so not built")
 def test_ctypes_table_matches_header():
+    """fervit/_lib.py against include/fervit.h: the same entry points; per entry point the same return
+    type, parameter count and, position by position, kind and width; per mirrored struct the same fields
+    in the same order with the same types, offsets and size. Every prototype and every struct of the header
+    is covered: one the parser cannot read fails here."""
+    from fervit import _lib
     from fervit._lib import SIGNATURES, lib
 
     L = lib()
     assert set(SIGNATURES) == set(declared())
     assert L.fer_version().decode().startswith("fervit")
+
+    mirrors = {"fer_gemm_desc": _lib.GemmDesc, "fer_epilogue": _lib.Epilogue, "fer_wgrad_item": _lib.WgradItem,
+               "fer_adamw_segment": _lib.AdamWSegment, "fer_image_aug": _lib.ImageAug}
+    structs = header_structs()
+    assert set(structs) == set(mirrors)
+    in_lib = {v for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, ctypes.Structure)
+              and v is not ctypes.Structure}
+    assert in_lib == set(mirrors.values()), "a ctypes.Structure of _lib.py has no struct of the header behind it"
+    bad = []
+    for name, fields in structs.items():
+        S = mirrors[name]
+        if [f for f, _, _ in fields] != [f for f, _ in S._fields_]:
+            bad.append(f"{name}: field order: header {[f for f, _, _ in fields]}, {S.__name__} {[f for f, _ in S._fields_]}")
+            continue
+        offs, size = natural_layout(fields)
+        for (f, base, depth), (_, ct), off in zip(fields, S._fields_, offs):
+            want = type_mismatch(base, depth, ct, mirrors)
+            if want:
+                bad.append(f"{name}.{f}: header {want}, {S.__name__} {ct.__name__}")
+            elif getattr(S, f).offset != off:
+                bad.append(f"{name}.{f}: offset {off} in C, {getattr(S, f).offset} in {S.__name__}")
+        if ctypes.sizeof(S) != size:
+            bad.append(f"{name}: sizeof {size} in C, {ctypes.sizeof(S)} in {S.__name__}")
+
+    protos = header_prototypes()
+    assert set(protos) == set(SIGNATURES)
+    returns = {("int", 0): ctypes.c_int, ("int64_t", 0): ctypes.c_int64, ("char", 1): ctypes.c_char_p}
+    for name, (ret, params) in protos.items():
+        res, args = SIGNATURES[name]
+        assert ret in returns, f"{name}: no ctypes counterpart known for its return type {ret}"
+        if res is not returns[ret]:
+            bad.append(f"{name}: returns {ret[0] + '*' * ret[1]}, table {res.__name__}")
+        if len(params) != len(args):
+            bad.append(f"{name}: {len(params)} parameters in the header, {len(args)} in the table")
+            continue
+        for i, ((p, base, depth), ct) in enumerate(zip(params, args)):
+            want = type_mismatch(base, depth, ct, mirrors)
+            if want:
+                bad.append(f"{name} argument {i} ({p}): header {want}, table {ct.__name__}")
+    assert not bad, "\n".join(["fervit/_lib.py disagrees with include/fervit.h:"] + bad)
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libfervit.so not built")
@@ -62,8 +184,7 @@ def test_gemm_set_config_accepts_only_the_kept_configurations():
 
 def dtype_entries():
     """Entry points whose first parameter is the dtype code (include/fervit.h spells it `int dtype`)."""
-    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(fer_[a-z0-9_]+)\s*\(\s*int\s+dtype\b", src)))
+    return sorted(set(re.findall(r"\b(fer_[a-z0-9_]+)\s*\(\s*int\s+dtype\b", header())))
 
 
 def zero_args(argtypes, dtype, **over):
@@ -120,7 +241,6 @@ def test_valid_dtype_with_an_empty_shape_still_returns_zero(dtype):
 
 def test_integration_doc_names_only_declared_symbols():
     """Every fer_* identifier INTEGRATION.md names is declared in include/fervit.h."""
-    hdr = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    known = set(re.findall(r"\bfer_[a-z0-9_]+", hdr))
+    known = set(re.findall(r"\bfer_[a-z0-9_]+", header()))
     named = set(re.findall(r"\bfer_[a-z0-9_]+", open(os.path.join(ROOT, "INTEGRATION.md")).read()))
     assert named and not sorted(named - known), sorted(named - known)

@@ -21,88 +21,20 @@ w x 30 (near one-hot, small probabilities underflow), x + 100 with sum(w) != 0 (
 without the max subtraction). Every output is a view into a NaN-filled parent with guard rows and, in the
 padded run, padded strides; the padding must keep its bits and the results hold no NaN. Each call runs
 twice (bit-identical repeat); probs = null gives the same y bits."""
-import numpy as np
 import pytest
 import torch
 
 import cnn_deep_ref as D
+from abi_harness import (all_nan, exact, f32v, last_error, lib, nanvec, nanview, ops, ptr, tdt, untouched,
+                         untouched_vec)
 from dropmask import keep_mask
 from elemwise import BF_ROUND, U, assert_bits_equal, assert_close, measure_c
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD = 2
 F64 = torch.float64
 KINDS = ("randn", "nobias", "const", "sharp", "shift")
-
-
-def ops():
-    from fervit import ops as o
-
-    return o
-
-
-def lib():
-    from fervit._lib import lib as l_
-
-    return l_()
-
-
-def last_error():
-    return lib().fer_last_error().decode()
-
-
-def tdt(dtype):
-    return torch.bfloat16 if dtype == "bf16" else torch.float32
-
-
-def f32v(v):
-    return float(np.float32(v))
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def nanview(rows, cols, pad, dt, src=None):
-    """[rows][cols] view inside a NaN-filled parent with GUARD rows above and below and `pad` extra columns."""
-    parent = torch.full((rows + 2 * GUARD, cols + pad), float("nan"), dtype=dt, device=DEV)
-    v = parent[GUARD:GUARD + rows, :cols]
-    if src is not None:
-        v.copy_(src.to(dt))
-    assert v.data_ptr() % 16 == 0
-    return v, parent
-
-
-def nanvec(n):
-    """[n] fp32 view inside a NaN-filled parent with 4 guard elements on each side (16-byte aligned)."""
-    parent = torch.full((n + 8,), float("nan"), dtype=torch.float32, device=DEV)
-    return parent[4:4 + n], parent
-
-
-def untouched(name, parent, rows, cols):
-    a = parent.clone()
-    a[GUARD:GUARD + rows, :cols] = 0
-    b = torch.full_like(parent, float("nan"))
-    b[GUARD:GUARD + rows, :cols] = 0
-    assert_bits_equal(name + " padding", a, b)
-
-
-def untouched_vec(name, parent, n):
-    a = parent.clone()
-    a[4:4 + n] = 0
-    b = torch.full_like(parent, float("nan"))
-    b[4:4 + n] = 0
-    assert_bits_equal(name + " guards", a, b)
-
-
-def all_nan(name, parent):
-    assert_bits_equal(name + " untouched", parent, torch.full_like(parent, float("nan")))
-
-
-def exact(v):
-    return v.float().cpu().double()
 
 
 def close(name, got, ref, scale, c, out_round):
@@ -217,8 +149,7 @@ def pool_case(dtype, B, L, C, kind):
         bruns = []
         for _ in range(2):
             dxd, dxp = nanview(B * L, C, pad, dt)
-            dwp = torch.full((B + 2 * GUARD, C), float("nan"), device=DEV)
-            dwd = dwp[GUARD:GUARD + B]
+            dwd, dwp = nanview(B, C, 0, torch.float32)
             dbv, dbp = nanvec(B)
             assert call_bwd(dyd, xd, wd, pv, dxd, dwd, dbv, B, L, C) == 0, last_error()
             bruns.append((dxp, dwp, dbp, dxd, dwd, dbv))

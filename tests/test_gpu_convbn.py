@@ -17,11 +17,12 @@ Elements whose pre-ReLU value lies within its own bound of 0 are left out (the g
 way), in the backward together with their column's sums; the reference must leave out <= 0.1 %."""
 import functools
 
-import numpy as np
 import pytest
 import torch
 
 import cnn_ref as R
+from abi_harness import all_nan, exact, f32v, last_error, nanview, ops, ptr, tdt, untouched
+from abi_harness import lib as L
 from dropmask import keep_mask
 from elemwise import BF_ROUND, U, assert_bits_equal, assert_close, measure_c
 
@@ -30,62 +31,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GUARD = 2
 F64 = torch.float64
-
-
-def ops():
-    from fervit import ops as o
-
-    return o
-
-
-def L():
-    from fervit._lib import lib
-
-    return lib()
-
-
-def last_error():
-    return L().fer_last_error().decode()
-
-
-def tdt(dtype):
-    return torch.bfloat16 if dtype == "bf16" else torch.float32
-
-
-def f32v(v):
-    return float(np.float32(v))
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def nanview(rows, cols, pad, dt, src=None):
-    """[rows][cols] view inside a NaN-filled parent with GUARD rows above and below and `pad` extra columns."""
-    parent = torch.full((rows + 2 * GUARD, cols + pad), float("nan"), dtype=dt, device=DEV)
-    v = parent[GUARD:GUARD + rows, :cols]
-    if src is not None:
-        v.copy_(src.to(dt))
-    assert v.data_ptr() % 16 == 0
-    return v, parent
-
-
-def untouched(name, parent, rows, cols):
-    """Everything outside the view still holds the parent's NaN bits."""
-    a = parent.clone()
-    a[GUARD:GUARD + rows, :cols] = 0
-    b = torch.full_like(parent, float("nan"))
-    b[GUARD:GUARD + rows, :cols] = 0
-    assert_bits_equal(name + " padding", a, b)
-
-
-def all_nan(name, parent):
-    assert_bits_equal(name + " untouched", parent, torch.full_like(parent, float("nan")))
-
-
-def exact(v):
-    """The float64 values a device tensor holds."""
-    return v.float().cpu().double()
 
 
 # ---------------------------------------------------------------------- conv1d im2col

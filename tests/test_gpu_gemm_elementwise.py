@@ -28,12 +28,13 @@ import functools
 import math
 import types
 
-import numpy as np
 import pytest
 import torch
 
+from abi_harness import f32v, last_error, nanview, ops, out_round, tdt
+from abi_harness import lib as L
 from dropmask import keep_mask, keep_mask_torch
-from elemwise import BF_ROUND, U, assert_bits_equal, assert_close, measure_c
+from elemwise import U, assert_bits_equal, assert_close, measure_c
 
 pytestmark = pytest.mark.gpu
 
@@ -47,35 +48,6 @@ ACT = {"none": 0, "gelu": 1, "relu": 2, "mul": 3}
 PRE_GATE = 16
 LAYOUTS = [(1, 1), (1, 0), (0, 0), (0, 1)]
 CFGS = [3, 5, 8, 11]
-
-
-def ops():
-    from fervit import ops as o
-
-    return o
-
-
-def L():
-    from fervit._lib import lib
-
-    return lib()
-
-
-def last_error():
-    return L().fer_last_error().decode()
-
-
-def tdt(dtype):
-    return torch.bfloat16 if dtype == "bf16" else torch.float32
-
-
-def f32v(v):
-    """The fp32 value a `float` argument of the C ABI carries."""
-    return float(np.float32(v))
-
-
-def out_round_of(dt):
-    return BF_ROUND if dt == torch.bfloat16 else 0.0
 
 
 class forced_config:
@@ -119,11 +91,7 @@ class Out:
 
 def inp(src, pad, dt):
     """An input as the column-0 view of a parent whose `pad` padding columns are NaN."""
-    rows, cols = src.shape
-    parent = torch.full((rows, cols + pad), float("nan"), dtype=dt, device=DEV)
-    v = parent[:, :cols]
-    v.copy_(src.to(dt))
-    return v
+    return nanview(*src.shape, pad, dt, src, guard=0)[0]
 
 
 # ---------------------------------------------------------------------- raw ABI call
@@ -353,13 +321,13 @@ def run_case(tag, sp, *, via="raw", dev="cpu", strides=(False, True), repeat=Fal
         c, pre, col = fresh()
         call(c, pre, col)
         got_c = c.view.float().cpu()
-        assert_close(f"{name} c", got_c, r.c, eff(r.s_c, r.a_c, cs["c"]), cs["c"], out_round_of(odt))
+        assert_close(f"{name} c", got_c, r.c, eff(r.s_c, r.a_c, cs["c"]), cs["c"], out_round(odt))
         c.check_guards(f"{name} c")
         if pre is not None:
             got_p = pre.view.float().cpu()
             if out is not None:
                 got_p = torch.where(out, r.pre.float(), got_p)
-            assert_close(f"{name} pre", got_p, r.pre, eff(r.s_pre, r.a_pre, cs["pre"]), cs["pre"], out_round_of(dt))
+            assert_close(f"{name} pre", got_p, r.pre, eff(r.s_pre, r.a_pre, cs["pre"]), cs["pre"], out_round(dt))
             pre.check_guards(f"{name} pre")
         if col is not None:
             assert_close(f"{name} colsum", col.view[0], r.colsum, eff(r.s_colsum, r.a_colsum, cs["colsum"]),
@@ -367,7 +335,7 @@ def run_case(tag, sp, *, via="raw", dev="cpu", strides=(False, True), repeat=Fal
             col.check_guards(f"{name} colsum")
         if sp.p > 0 and sp.act != "relu" and sp.aux is None and not sp.res and not sp.accumulate:
             # keep decisions: exactly 0 iff the host mask drops, where the kept value is above its own bound
-            bound = out_round_of(odt) * r.kept.abs() + cs["c"] * U * r.s_kept + r.a_kept
+            bound = out_round(odt) * r.kept.abs() + cs["c"] * U * r.s_kept + r.a_kept
             live = r.kept.abs() > bound
             assert live.double().mean().item() >= 0.99, f"{name}: live set {live.double().mean().item():.4f}"
             wrong = ((got_c != 0) != t.keep) & live

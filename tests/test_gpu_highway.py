@@ -11,32 +11,14 @@ import pytest
 import torch
 
 import afs_ref as R
-from elemwise import BF_ROUND, assert_bits_equal, assert_close, measure_c
+from abi_harness import NAN, out_round, parent, untouched_parent
+from elemwise import assert_bits_equal, assert_close, measure_c
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
-NAN = float("nan")
 EPS = 1e-5
 KINDS = ["randn", "const_col", "plus100", "gate30", "neg_n"]
-
-
-def out_round(dt):
-    return BF_ROUND if dt == torch.bfloat16 else 0.0
-
-
-def parent(G, rows, cols, dtype, data=None):
-    p = torch.full((G, rows + 2, cols + 8), NAN, dtype=dtype, device=DEV)
-    v = p[:, 1:-1, :cols]
-    if data is not None:
-        v.copy_(data)
-    return p, v
-
-
-def untouched(p, cols):
-    q = p.clone()
-    q[:, 1:-1, :cols] = NAN
-    return bool(q.isnan().all())
 
 
 def vecs(G, n, data=None, dtype=torch.float32):
@@ -120,7 +102,7 @@ def run_native(d, dtype, train, act, momentum):
     dgam.fill_(NAN)
     dbet.fill_(NAN)
     dpn, dpl, dpg = ops.highway_bwd(dy, pn, pl, pg, mean, rstd, gamma, beta, train, act, dgamma=dgam, dbeta=dbet)
-    assert untouched(py, C), "highway_fwd wrote outside y"
+    untouched_parent("highway_fwd y", py, C)
     return dict(y=y, mean=mean, rstd=rstd, rm=rm, rv=rv, dpn=dpn, dpl=dpl, dpg=dpg, dgamma=dgam, dbeta=dbet, nbt=nbt)
 
 

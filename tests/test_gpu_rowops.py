@@ -21,6 +21,8 @@ import numpy as np
 import pytest
 import torch
 
+from abi_harness import f32v, last_error, nanview, ops, ptr, tdt, untouched
+from abi_harness import lib as L
 from dropmask import keep_mask
 from elemwise import BF_ROUND, U, assert_bits_equal, assert_close, measure_c  # noqa: F401
 
@@ -28,31 +30,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 BIG = 8192 * 256 + 3  # past the 8192-block grid cap of the element kernels: grid-stride loop
-
-
-def ops():
-    from fervit import ops as o
-
-    return o
-
-
-def L():
-    from fervit._lib import lib
-
-    return lib()
-
-
-def last_error():
-    return L().fer_last_error().decode()
-
-
-def tdt(dtype):
-    return torch.bfloat16 if dtype == "bf16" else torch.float32
-
-
-def f32v(v):
-    """The fp32 value a `float` argument of the C ABI carries."""
-    return float(np.float32(v))
 
 
 def cu_count():
@@ -125,25 +102,6 @@ def ln_inputs(M, D, Lr, seed):
     return x, gam, bet, dy, res
 
 
-def padded(src, M, D, pad, dt):
-    """A [M][D] view from column 0 of a NaN-filled [M][D + pad] tensor (16-byte aligned base)."""
-    parent = torch.full((M, D + pad), float("nan"), dtype=dt, device=DEV)
-    v = parent[:, :D]
-    if src is not None:
-        v.copy_(src.to(dt))
-    assert v.data_ptr() % 16 == 0 and v.stride(0) == D + pad
-    return v, parent
-
-
-def pad_untouched(name, parent, D):
-    if parent.shape[1] > D:
-        assert torch.isnan(parent[:, D:]).all().item(), f"{name}: the kernel wrote outside [:, :D]"
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def call_ln_fwd(x, gam, bet, Lr, row_div, y, mean, rstd, M, D, eps):
     o = ops()
     return L().fer_layernorm_fwd(o.dcode(x), x.data_ptr(), x.stride(0), gam.data_ptr(), bet.data_ptr(), Lr, row_div,
@@ -174,9 +132,9 @@ def run_ln(dtype, M, D, *, Lr=1, row_div=1, eps=1e-5, pads=None, use_res=True, p
     pads = dict(dict(x=0, y=0, dy=0, res=0, dx=0), **(pads or {}))
     x0, gam, bet, dy0, res0 = inputs if inputs is not None else ln_inputs(M, D, Lr, 1000 * D + M)
     eps = f32v(eps)
-    xd, _ = padded(x0, M, D, pads["x"], dt)
-    dyd, _ = padded(dy0, M, D, pads["dy"], dt)
-    resd = padded(res0, M, D, pads["res"], dt)[0] if use_res else None
+    xd, _ = nanview(M, D, pads["x"], dt, x0, guard=0)
+    dyd, _ = nanview(M, D, pads["dy"], dt, dy0, guard=0)
+    resd = nanview(M, D, pads["res"], dt, res0, guard=0)[0] if use_res else None
     gd, bd = gam.to(DEV).contiguous(), bet.to(DEV).contiguous()
     # the exact values the kernels see
     x, dy = xd.float().cpu().double(), dyd.float().cpu().double()
@@ -185,7 +143,7 @@ def run_ln(dtype, M, D, *, Lr=1, row_div=1, eps=1e-5, pads=None, use_res=True, p
     G, Bt = gam.double()[gi], bet.double()[gi]
 
     # ---- forward
-    yd, yp = padded(None, M, D, pads["y"], dt)
+    yd, yp = nanview(M, D, pads["y"], dt, guard=0)
     mean = torch.full((M,), float("nan"), device=DEV)
     rstd = torch.full((M,), float("nan"), device=DEV)
     rc = call_ln_fwd(xd, gd, bd, Lr, row_div, yd, mean if want_stats else None, rstd if want_stats else None, M, D,
@@ -200,7 +158,7 @@ def run_ln(dtype, M, D, *, Lr=1, row_div=1, eps=1e-5, pads=None, use_res=True, p
     c_mean = measure_c(f"{tag}.mean", dtype, [(t32["mean"], fr["mean"], fr["s_mean"])])
     c_rstd = measure_c(f"{tag}.rstd", dtype, [(t32["rstd"], fr["rstd"], fr["s_rstd"])])
     assert_close(f"{tag}.y", yd, fr["y"], fr["s_y"], c_y, out_round)
-    pad_untouched(f"{tag}.y", yp, D)
+    untouched(f"{tag}.y", yp, M, D, guard=0)
     if want_stats:
         assert_close(f"{tag}.mean", mean, fr["mean"], fr["s_mean"], c_mean, 0.0)
         assert_close(f"{tag}.rstd", rstd, fr["rstd"], fr["s_rstd"], c_rstd, 0.0)
@@ -212,8 +170,8 @@ def run_ln(dtype, M, D, *, Lr=1, row_div=1, eps=1e-5, pads=None, use_res=True, p
         assert_bits_equal(f"{tag}.y with / without saved statistics", y2, yd.contiguous())
 
     # ---- backward
-    dxv, dxp = padded(None, M, D, pads["dx"], dt)
-    dxdv, dxdp = padded(None, M, D, pads["dx"], dt) if use_dxd else (None, None)
+    dxv, dxp = nanview(M, D, pads["dx"], dt, guard=0)
+    dxdv, dxdp = nanview(M, D, pads["dx"], dt, guard=0) if use_dxd else (None, None)
     g0 = torch.Generator().manual_seed(5)
     init = {k: (torch.randn(D, generator=g0) * 3 if accumulate else torch.full((D,), float("nan"))) for k in GRADS}
     gout = {k: (init[k].clone().to(DEV) if k in want else None) for k in GRADS}
@@ -226,11 +184,11 @@ def run_ln(dtype, M, D, *, Lr=1, row_div=1, eps=1e-5, pads=None, use_res=True, p
     bx = ln_bwd_ref(x, dy, G, res, fr["mean"], fr["rstd"], keep, sc)
     c_dx = measure_c(f"{tag}.dx", dtype, [(t32["dx"], bx["dx"], bx["s_dx"])])
     assert_close(f"{tag}.dx", dxv, br["dx"], br["s_dx"], c_dx, out_round)
-    pad_untouched(f"{tag}.dx", dxp, D)
+    untouched(f"{tag}.dx", dxp, M, D, guard=0)
     if use_dxd:
         c_dxd = measure_c(f"{tag}.dx_drop", dtype, [(t32["dxd"], bx["dxd"], bx["s_dxd"])])
         assert_close(f"{tag}.dx_drop", dxdv, br["dxd"], br["s_dxd"], c_dxd, out_round)
-        pad_untouched(f"{tag}.dx_drop", dxdp, D)
+        untouched(f"{tag}.dx_drop", dxdp, M, D, guard=0)
         if p == 0:
             assert_bits_equal(f"{tag}.dx_drop at p = 0 vs dx", dxdv.contiguous(), dxv.contiguous())
         elif keep_check:
@@ -610,7 +568,7 @@ def test_colsum(dtype, M, N):
     live lane per block; 252, 768: one and three column blocks."""
     o = ops()
     g = torch.Generator().manual_seed(M * 1000 + N)
-    xv, _ = padded(torch.randn(M, N, generator=g), M, N, 4, tdt(dtype))
+    xv, _ = nanview(M, N, 4, tdt(dtype), torch.randn(M, N, generator=g), guard=0)
     x = xv.float().cpu().double()
     ref, scale = x.sum(0), x.abs().sum(0)
     f32 = xv.float().cpu().sum(0)
