@@ -1,5 +1,6 @@
 """The harness the element-wise kernel tests share (tests/test_gpu_convbn.py, test_gpu_attnpool.py,
-test_gpu_rowops.py, test_gpu_gemm_elementwise.py, test_gpu_grouped_gemm.py, test_gpu_highway.py): access to the
+test_gpu_rowops.py, test_gpu_gemm_elementwise.py, test_gpu_grouped_gemm.py, test_gpu_highway.py,
+test_gpu_attention_elementwise.py): access to the
 C ABI, and operands as views into NaN-filled parents whose guard rows and padding columns must keep their
 bits. The bound arithmetic is tests/elemwise.py.
 
