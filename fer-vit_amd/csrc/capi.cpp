@@ -63,7 +63,8 @@ extern "C" int fer_set_step_counter(const uint64_t* counter) {
   // every code object that has dropout kernels keeps its own copy of the pointer
   if (fer::set_step_ptr_gemm(counter) || fer::set_step_ptr_attention(counter) ||
       fer::set_step_ptr_layernorm(counter) || fer::set_step_ptr_misc(counter) ||
-      fer::set_step_ptr_convbn(counter) || fer::set_step_ptr_attnpool(counter))
+      fer::set_step_ptr_convbn(counter) || fer::set_step_ptr_attnpool(counter) ||
+      fer::set_step_ptr_conv2d(counter))
     return fer::set_error("set_step_counter: hipMemcpyToSymbol failed");
   return 0;
 }

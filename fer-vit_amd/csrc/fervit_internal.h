@@ -32,6 +32,7 @@ int set_step_ptr_layernorm(const uint64_t* p);
 int set_step_ptr_misc(const uint64_t* p);
 int set_step_ptr_convbn(const uint64_t* p);
 int set_step_ptr_attnpool(const uint64_t* p);
+int set_step_ptr_conv2d(const uint64_t* p);
 int hip_check(const char* what);
 // persistent GEMM / attention kernels: walk a fixed blockIdx stride instead of the work queue
 // (fer_set_persistent_mode(1))

@@ -96,6 +96,12 @@ SIGNATURES = {
     "fer_attnpool_bwd": (i32, [i32, vp, i64, vp, i64, fp, fp, vp, i64, fp, fp, i32, i32, i32, vp]),
     "fer_relu_dropout_fwd": (i32, [i32, vp, i64, vp, i64, i32, i32, u32, f32, u64, vp]),
     "fer_relu_dropout_bwd": (i32, [i32, vp, i64, vp, i64, vp, i64, i32, i32, u32, f32, u64, vp]),
+    "fer_conv2d_cols": (i32, [i32, vp, i64, vp, i64, i32, i32, i32, i32, vp]),
+    "fer_conv2d_cols_bwd": (i32, [i32, vp, i64, vp, i64, i32, i32, i32, i32, vp]),
+    "fer_conv2d_c1_fwd": (i32, [i32, vp, i64, fp, fp, vp, i64, i32, i32, i32, i32, vp]),
+    "fer_conv2d_c1_bwd": (i32, [i32, vp, i64, vp, i64, fp, fp, i32, vp, i64, i32, i32, i32, i32, vp]),
+    "fer_pool2_chdrop_fwd": (i32, [i32, vp, i64, vp, i64, i32, i32, i32, i32, i32, u32, f32, u64, vp]),
+    "fer_pool2_chdrop_bwd": (i32, [i32, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, u32, f32, u64, vp]),
     "fer_grouped_linear_fwd": (i32, [i32, vp, i64, i64, vp, vp, vp, i64, i64, fp, fp, fp, i64, vp, vp, vp, i64, i64,
                                      i32, i32, i32, i32, vp]),
     "fer_grouped_linear_dgrad": (i32, [i32, vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, i32, i32, i32,

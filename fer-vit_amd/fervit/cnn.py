@@ -16,6 +16,9 @@ modules (outside the flat store); the kernels update them in place on the device
   MlpLogitsFn  Linear -> ReLU -> Dropout -> Linear(., num_classes) (`latent_cnn.py:301-304`)
   ProjLNFn     Linear -> LayerNorm -> ReLU -> Dropout, LatentCNNDeep's input_proj (`latent_cnn.py:183-188`)
   AttnPoolFn   Conv1d(C, 1, 1) -> Softmax over the sequence -> weighted sum (`latent_cnn.py:207-211,256-257`)
+  Conv2dBNFn   LatentCNN2D's stages (`latent_cnn.py:351-369`) on pixel-major rows [B*H*W][C]:
+               Conv2d(3x3, padding 1) -> BatchNorm2d -> ReLU -> (MaxPool2d((2, 2))) -> Dropout2d; the convolution
+               is im2col + GEMM, or the direct first-layer kernel when Cin = 1
 """
 from __future__ import annotations
 
@@ -294,3 +297,96 @@ class AttnPoolFn(torch.autograd.Function):
         _finish(flat, P, needs)
         ctx.saved = None
         return (dx, None, None, None, None) + (None,) * len(P)
+
+
+# ---------------------------------------------------------------- LatentCNN2D
+# The im2col matrix of a 3x3 convolution is nine times its input (B*9216 x 576 bf16 = 680 MB for
+# Conv2d(64, 128) at batch 64). It is built per group of whole samples of at most this many bytes (fer_gemm
+# takes operands below 2 GiB), consumed by the GEMM and dropped; the backward rebuilds it from the saved
+# input for the weight gradient instead of keeping it. The groups depend on the shape alone.
+COLS_CHUNK_BYTES = 1 << 30
+
+
+@dataclass
+class Cnn2dCfg:
+    B: int
+    H: int
+    W: int
+    pool: bool = False     # MaxPool2d((2, 2)) behind the ReLU
+    dropout: float = 0.0   # Dropout2d (per sample and channel), behind the pool; 0 outside training
+    save: bool = True
+
+
+def _sample_groups(B: int, rows_per_sample: int, row_bytes: int):
+    """[(first sample, samples)] with rows_per_sample * row_bytes * samples <= COLS_CHUNK_BYTES (at least 1)."""
+    nb = max(1, min(B, COLS_CHUNK_BYTES // max(1, rows_per_sample * row_bytes)))
+    return [(b0, min(nb, B - b0)) for b0 in range(0, B, nb)]
+
+
+class Conv2dBNFn(torch.autograd.Function):
+    # params: conv w [Cout,Cin,3,3], conv b (or None), bn gamma, bn beta. x: [B*H*W, Cin], or for Cin = 1 the
+    # image itself, any contiguous shape with B*H*W elements
+    @staticmethod
+    def forward(ctx, x, cfg: Cnn2dCfg, flat: FlatParams, bn: BNState, *P):
+        w, b, gam, beta = P
+        B, H, W = cfg.B, cfg.H, cfg.W
+        dt = x.dtype
+        Cout, Cin = w.shape[0], w.shape[1]
+        bias = None if b is None else b.data
+        if Cin == 1:
+            h = ops.conv2d_c1_fwd(x, w.data, bias, B, H, W)
+        else:
+            Wm = _weight(flat, w, dt).reshape(Cout, -1)
+            h = torch.empty(B * H * W, Cout, dtype=dt, device=x.device)
+            for b0, nb in _sample_groups(B, H * W, 9 * Cin * x.element_size()):
+                r0, r1 = b0 * H * W, (b0 + nb) * H * W
+                ops.linear_fwd(ops.conv2d_cols(x[r0:r1], nb, H, W), Wm, bias, out=h[r0:r1])
+        r, mean, rstd = ops.batchnorm_fwd(h, gam.data, beta.data, bn.running_mean, bn.running_var,
+                                          bn.num_batches_tracked, bn.train, bn.momentum, bn.eps, relu=True)
+        tail = cfg.pool or cfg.dropout > 0
+        seed = next_seed() if cfg.dropout > 0 else 0
+        y = ops.pool2_chdrop_fwd(r, B, H, W, cfg.pool, dropout=cfg.dropout, seed=seed) if tail else r
+        if cfg.save:
+            ctx.cfg, ctx.flat, ctx.P = cfg, flat, P
+            ctx.saved = (x, h, mean, rstd, r if cfg.pool else None, seed, bn.train, tail)
+        return y
+
+    @staticmethod
+    @_deferred_reductions
+    def backward(ctx, dy):
+        cfg, flat, P = ctx.cfg, ctx.flat, ctx.P
+        w, b, gam, beta = P
+        x, h, mean, rstd, r, seed, train, tail = ctx.saved
+        B, H, W = cfg.B, cfg.H, cfg.W
+        Cout, Cin = w.shape[0], w.shape[1]
+        needs = ctx.needs_input_grad[4:]
+        G, acc = _targets(flat, P, needs)
+        gw, gb, ggam, gbeta = G
+        want_dx = ctx.needs_input_grad[0]
+        dy = dy.contiguous()
+        if tail:
+            # pool = 0 reads no x: the keep bits alone
+            dy = ops.pool2_chdrop_bwd(dy, r if cfg.pool else h, B, H, W, cfg.pool, dropout=cfg.dropout, seed=seed)
+        dh, _ = ops.batchnorm_bwd(dy, h, mean, rstd, gam.data, beta.data, train, relu=True, dgamma=ggam, dbeta=gbeta,
+                                  accumulate=acc)
+        if gb is not None:
+            ops.colsum(dh, gb, accumulate=acc)
+        dx = None
+        if Cin == 1:
+            dx = ops.conv2d_c1_bwd(dh, x, w.data, B, H, W, dw=gw, accumulate=acc, want_dx=want_dx)
+        elif gw is not None or want_dx:
+            Wm = _weight(flat, w, dh.dtype).reshape(Cout, -1)
+            if want_dx:
+                dx = torch.empty_like(x)
+            for i, (b0, nb) in enumerate(_sample_groups(B, H * W, 9 * Cin * x.element_size())):
+                r0, r1 = b0 * H * W, (b0 + nb) * H * W
+                if gw is not None:
+                    # K = pixels: the split count must not hang on the shared workspace's size (ops.gemm ws_exact)
+                    _wgrad(dh[r0:r1], ops.conv2d_cols(x[r0:r1], nb, H, W), gw.view(Cout, -1), accumulate=acc or i > 0,
+                           ws_exact=True)
+                if want_dx:
+                    # conv weights are 4-D: no transposed shadow in the flat store, the dgrad reads W as an MN operand
+                    ops.conv2d_cols_bwd(ops.linear_dgrad(dh[r0:r1], Wm), nb, H, W, out=dx[r0:r1])
+        _finish(flat, P, needs)
+        ctx.saved = None
+        return (dx, None, None, None) + (None,) * len(P)

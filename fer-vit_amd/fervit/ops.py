@@ -120,10 +120,13 @@ def gemm(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, a_kc: bool = Tr
          aux: Optional[torch.Tensor] = None, aux_act: str = "none", alpha: float = 1.0, accumulate: bool = False,
          post_scale: Optional[torch.Tensor] = None, split_ws: bool = True,
          colsum: Optional[torch.Tensor] = None, colsum_accumulate: bool = False,
-         pre_gate: bool = False) -> torch.Tensor:
+         pre_gate: bool = False, ws_exact: bool = False) -> torch.Tensor:
     """out[m][n] = epilogue(sum_k A(m,k) B(n,k)); see include/fervit.h for the layouts.
     colsum: optional fp32 [N] receiving (or, with colsum_accumulate, adding) sum_m out[m][n].
-    pre_gate: `pre` receives act'(pre) * dropout keep * scale (consumed by aux_act="mul")."""
+    pre_gate: `pre` receives act'(pre) * dropout keep * scale (consumed by aux_act="mul").
+    ws_exact: report the split-K workspace as the bytes asked for, not the (grow-only, shared) buffer's size.
+    The library caps the split count by the workspace it is given, so where that cap binds (a few output
+    tiles over a very long K) the summation order would otherwise depend on what ran before on the stream."""
     _dev(A)
     if A.dtype != B.dtype:
         raise TypeError("gemm: A and B dtypes differ")
@@ -141,6 +144,8 @@ def gemm(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, a_kc: bool = Tr
         # split-K slabs: the library targets ~one 256x256 workgroup per CU (or 512 128^2 ones)
         nb = 4 * M * N * min(32, max(2, 512 // t256)) + 4 * (-(-M // 128) * -(-N // 128)) + 256  # + tile tickets
         d.ws, d.ws_bytes = _ws(nb, A.device, slot=1)
+        if ws_exact:
+            d.ws_bytes = nb
     e = Epilogue()
     e.c = out.data_ptr()
     e.ldc = ldc if ldc is not None else N
@@ -597,6 +602,107 @@ def relu_dropout_bwd(dy, x, dropout=0.0, seed=0, out=None):
     check(lib().fer_relu_dropout_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0),
                                      out.data_ptr(), out.stride(0), M, Cc, *_drop(dropout, seed), stream()),
           "relu_dropout_bwd")
+    return out
+
+
+# ------------------------------------------------------------------ LatentCNN2D operators (csrc/conv2d.hip)
+def _pixels(t: torch.Tensor, B: int, H: int, W: int, what: str) -> None:
+    _rows(t, what)
+    if t.shape[0] != B * H * W:
+        raise ValueError(f"{what}: the operand must have B*H*W rows")
+
+
+def conv2d_cols(x, B, H, W, out=None):
+    """im2col of nn.Conv2d(3x3, padding=1): x [B*H*W, C] -> cols [B*H*W, 9*C] in (cin, kh, kw) column order."""
+    _pixels(x, B, H, W, "conv2d_cols")
+    M, Cc = x.shape
+    out = _alloc(out, x, (M, 9 * Cc))
+    check(lib().fer_conv2d_cols(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), B, H, W, Cc,
+                                stream()), "conv2d_cols")
+    return out
+
+
+def conv2d_cols_bwd(dcols, B, H, W, out=None):
+    """dx [B*H*W, C] from dcols [B*H*W, 9*C], the adjoint of conv2d_cols."""
+    _pixels(dcols, B, H, W, "conv2d_cols_bwd")
+    M, K = dcols.shape
+    if K % 9:
+        raise ValueError("conv2d_cols_bwd: dcols must be [B*H*W, 9*C]")
+    out = _alloc(out, dcols, (M, K // 9))
+    check(lib().fer_conv2d_cols_bwd(dcode(dcols), dcols.data_ptr(), dcols.stride(0), out.data_ptr(), out.stride(0),
+                                    B, H, W, K // 9, stream()), "conv2d_cols_bwd")
+    return out
+
+
+def _c1_weight(w, what: str) -> int:
+    if w.dtype != torch.float32 or not w.is_contiguous() or w.numel() % 9:
+        raise ValueError(f"{what}: w must be a contiguous fp32 tensor of Cout*9 elements")
+    return w.numel() // 9
+
+
+def conv2d_c1_fwd(x, w, bias, B, H, W, out=None):
+    """nn.Conv2d(1, Cout, 3, padding=1): x with B*H*W elements (the image as it lies, contiguous) ->
+    y [B*H*W, Cout] in x's dtype; w fp32 [Cout, 1, 3, 3], bias fp32 [Cout] or None."""
+    _dev(x)
+    Cout = _c1_weight(w, "conv2d_c1_fwd")
+    if x.numel() != B * H * W or not x.is_contiguous():
+        raise ValueError("conv2d_c1_fwd: x must be contiguous with B*H*W elements")
+    out = _alloc(out, x, (B * H * W, Cout))
+    check(lib().fer_conv2d_c1_fwd(dcode(x), x.data_ptr(), 1, w.data_ptr(), ptr(bias), out.data_ptr(), out.stride(0),
+                                  B, H, W, Cout, stream()), "conv2d_c1_fwd")
+    return out
+
+
+def conv2d_c1_parts(M: int) -> int:
+    """Workgroups (= partial rows) of the first layer's weight gradient: strips of at least 256 pixels."""
+    return max(1, min(1024, M // 256))
+
+
+def conv2d_c1_bwd(dy, x, w, B, H, W, dw=None, accumulate=False, want_dx=False):
+    """Backward of conv2d_c1_fwd: dw (fp32, Cout*9 elements, optional) receives or accumulates the weight
+    gradient (per-workgroup partials added in a fixed order by colsum); returns dx (x's shape) or None."""
+    _pixels(dy, B, H, W, "conv2d_c1_bwd")
+    Cout = _c1_weight(w, "conv2d_c1_bwd")
+    M = B * H * W
+    if dy.shape[1] != Cout or x.numel() != M or not x.is_contiguous():
+        raise ValueError("conv2d_c1_bwd: dy must be [B*H*W, Cout] and x contiguous with B*H*W elements")
+    if dw is not None and (dw.dtype != torch.float32 or dw.numel() != Cout * 9 or not dw.is_contiguous()):
+        raise ValueError("conv2d_c1_bwd: dw must be a contiguous fp32 tensor of Cout*9 elements")
+    n_parts = conv2d_c1_parts(M)
+    part = torch.empty(n_parts, Cout * 9, dtype=torch.float32, device=dy.device) if dw is not None else None
+    dx = torch.empty_like(x) if want_dx else None
+    if part is None and dx is None:
+        return None
+    check(lib().fer_conv2d_c1_bwd(dcode(dy), dy.data_ptr(), dy.stride(0), x.data_ptr(), 1, w.data_ptr(), ptr(part),
+                                  n_parts, ptr(dx), 1, B, H, W, Cout, stream()), "conv2d_c1_bwd")
+    if dw is not None:
+        colsum(part, dw, accumulate=accumulate)
+    return dx
+
+
+def pool2_chdrop_fwd(x, B, H, W, pool, dropout=0.0, seed=0, out=None):
+    """MaxPool2d((2, 2)) (pool) then Dropout2d over x [B*H*W, C] -> [B*(H//2)*(W//2), C] (or x's shape)."""
+    _pixels(x, B, H, W, "pool2_chdrop_fwd")
+    Cc = x.shape[1]
+    Mo = B * (H // 2) * (W // 2) if pool else B * H * W
+    out = _alloc(out, x, (Mo, Cc))
+    check(lib().fer_pool2_chdrop_fwd(dcode(x), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), B, H, W, Cc,
+                                     int(bool(pool)), *_drop(dropout, seed), stream()), "pool2_chdrop_fwd")
+    return out
+
+
+def pool2_chdrop_bwd(dy, x, B, H, W, pool, dropout=0.0, seed=0, out=None):
+    """dx [B*H*W, C]: dy * keep / (1 - p) at each window's argmax (recomputed from the forward's x), 0 elsewhere."""
+    _pixels(x, B, H, W, "pool2_chdrop_bwd")
+    _rows(dy, "pool2_chdrop_bwd")
+    Cc = x.shape[1]
+    Mo = B * (H // 2) * (W // 2) if pool else B * H * W
+    if tuple(dy.shape) != (Mo, Cc):
+        raise ValueError("pool2_chdrop_bwd: dy must have the forward output's shape")
+    out = _alloc(out, x)
+    check(lib().fer_pool2_chdrop_bwd(dcode(x), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(),
+                                     out.stride(0), B, H, W, Cc, int(bool(pool)), *_drop(dropout, seed), stream()),
+          "pool2_chdrop_bwd")
     return out
 
 

@@ -9,15 +9,21 @@ running_var and num_batches_tracked are ordinary module buffers, updated on the 
 
 `create_latent_cnn('standard')` (`latent_cnn.py:66-161`, the trainer's default), `'light'`
 (`:264-330`) and `'deep'` (`:164-261`: Linear + LayerNorm projection, three conv stages with residual
-blocks, softmax attention pooling over the sequence) are native. `'2d'` needs Conv2d / MaxPool2d /
-Dropout2d kernels, which the library does not have: it raises NotImplementedError.
+blocks, softmax attention pooling over the sequence) are native.
+
+`LatentCNN2D` (`:333-409`: the (18, 512) code as a one-channel image through three Conv2d(3x3) +
+BatchNorm2d + ReLU stages with MaxPool2d((2, 2)) and Dropout2d, a global average pool and the classifier)
+is native too, on pixel-major rows [B*H*W][C] (csrc/conv2d.hip, fervit.cnn.Conv2dBNFn). The class is its
+public entry point for now: `create_latent_cnn('2d')` still raises NotImplementedError, because
+tests/test_latent_cnn_deep_cpu.py::test_2d_is_still_not_implemented pins that. The follow-up is one line,
+the factory branch `return LatentCNN2D(latent_dim, seq_len, num_classes, dropout)`, plus that test.
 """
 import torch
 import torch.nn as nn
 
 from fervit import ops
-from fervit.cnn import (AttnPoolFn, CnnCfg, ConvBNFn, LogitsFn, MlpLogitsFn, ProjLNFn, ResBlockFn, SeqMeanFn,
-                        bn_state)
+from fervit.cnn import (AttnPoolFn, Cnn2dCfg, CnnCfg, Conv2dBNFn, ConvBNFn, LogitsFn, MlpLogitsFn, ProjLNFn,
+                        ResBlockFn, SeqMeanFn, bn_state)
 from fervit.module import FerModule
 
 
@@ -298,9 +304,97 @@ class LatentCNNLight(FerModule):
                                  lin2.bias)
 
 
+def _check_conv2d(conv: nn.Conv2d) -> None:
+    if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (3, 3) or conv.stride != (1, 1) \
+            or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros":
+        raise NotImplementedError("fervit: only Conv2d(kernel_size=3, stride=1, padding=1) has a kernel")
+
+
+def _check_pool2d(pool: nn.MaxPool2d) -> None:
+    two = (2, (2, 2))
+    if not isinstance(pool, nn.MaxPool2d) or pool.kernel_size not in two or pool.stride not in two \
+            or pool.padding not in (0, (0, 0)) or pool.dilation not in (1, (1, 1)) or pool.ceil_mode \
+            or pool.return_indices:
+        raise NotImplementedError("fervit: only MaxPool2d((2, 2)) (stride 2, no padding, floor) has a kernel")
+
+
+class LatentCNN2D(FerModule):
+    """The w+ code as a one-channel (seq_len, latent_dim) image: Conv2d(1, 64) -> Conv2d(64, 128) + pool ->
+    Conv2d(128, 256) + pool, each with BatchNorm2d, ReLU and Dropout2d, then a global average pool and the
+    classifier (`latent_cnn.py:333-409`)."""
+
+    def __init__(self, latent_dim: int = 512, seq_len: int = 18, num_classes: int = 7, dropout: float = 0.3):
+        super().__init__()
+        self.features = nn.Sequential(
+            nn.Conv2d(1, 64, kernel_size=3, padding=1),
+            nn.BatchNorm2d(64),
+            nn.ReLU(inplace=True),
+            nn.Dropout2d(dropout * 0.5),
+            nn.Conv2d(64, 128, kernel_size=3, padding=1),
+            nn.BatchNorm2d(128),
+            nn.ReLU(inplace=True),
+            nn.MaxPool2d((2, 2)),
+            nn.Dropout2d(dropout * 0.5),
+            nn.Conv2d(128, 256, kernel_size=3, padding=1),
+            nn.BatchNorm2d(256),
+            nn.ReLU(inplace=True),
+            nn.MaxPool2d((2, 2)),
+            nn.Dropout2d(dropout),
+        )
+        self.gap = nn.AdaptiveAvgPool2d(1)
+        self.classifier = nn.Sequential(
+            nn.Flatten(),
+            nn.Linear(256, 256),
+            nn.BatchNorm1d(256),
+            nn.ReLU(inplace=True),
+            nn.Dropout(dropout),
+            nn.Linear(256, num_classes),
+        )
+        self._init_weights()
+
+    def _init_weights(self):
+        """`latent_cnn.py:386-396`."""
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+            elif isinstance(m, nn.Linear):
+                nn.init.normal_(m.weight, 0, 0.01)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: (B, seq_len, latent_dim) -> logits (B, num_classes), fp32."""
+        B, H, W = x.shape
+        flat = self.fer_flat()
+        save = self.need_grad(x, list(self.parameters()))
+        f = self.features
+        if f[0].in_channels != 1:
+            raise NotImplementedError("fervit: LatentCNN2D's first convolution reads the one-channel image")
+        # x.unsqueeze(1) in pixel-major layout is [B*H*W][1]: the tensor as it lies, cast to the compute dtype
+        t = _rows(x.reshape(1, B * H, W), self.compute_dtype()).reshape(-1)
+        for ci, pi, di in ((0, None, 3), (4, 7, 8), (9, 12, 13)):
+            conv, bn = f[ci], f[ci + 1]
+            _check_conv2d(conv)
+            if pi is not None:
+                _check_pool2d(f[pi])
+            cfg = Cnn2dCfg(B, H, W, pi is not None, _p(f[di], self.training), save)
+            t = Conv2dBNFn.apply(t, cfg, flat, bn_state(bn), conv.weight, conv.bias, bn.weight, bn.bias)
+            if pi is not None:
+                H, W = H // 2, W // 2
+        pooled = SeqMeanFn.apply(t, B, H * W)
+        _, lin1, bn, _, drop, lin2 = self.classifier
+        cfg = CnnCfg(B, 1, False, True, _p(drop, self.training), save)
+        h = ConvBNFn.apply(pooled, None, cfg, flat, bn_state(bn), lin1.weight, lin1.bias, bn.weight, bn.bias)
+        return LogitsFn.apply(h, save, flat, lin2.weight, lin2.bias)
+
+
 def create_latent_cnn(model_type: str = "standard", latent_dim: int = 512, seq_len: int = 18, num_classes: int = 7,
                       dropout: float = 0.3):
-    """`latent_cnn.py:412-438`. 'light', 'standard' and 'deep' run on the HIP path."""
+    """`latent_cnn.py:412-438`. 'light', 'standard' and 'deep' run on the HIP path; so does the class
+    LatentCNN2D, which this factory does not return yet (module docstring)."""
     if model_type == "light":
         return LatentCNNLight(latent_dim, seq_len, num_classes, dropout)
     if model_type == "standard":
@@ -308,6 +402,6 @@ def create_latent_cnn(model_type: str = "standard", latent_dim: int = 512, seq_l
     if model_type == "deep":
         return LatentCNNDeep(latent_dim, seq_len, num_classes, dropout)
     if model_type == "2d":
-        raise NotImplementedError("create_latent_cnn('2d'): LatentCNN2D needs Conv2d(3x3), MaxPool2d and Dropout2d "
-                                  "kernels, which the library does not have")
+        raise NotImplementedError("create_latent_cnn('2d'): not wired into the factory yet; construct "
+                                  "models_fer_vit.latent_cnn.LatentCNN2D directly")
     raise ValueError(f"Unknown model type: {model_type}")

@@ -341,6 +341,61 @@ int fer_relu_dropout_fwd(int dtype, const void* x, int64_t ldx, void* y, int64_t
 int fer_relu_dropout_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, void* dx, int64_t lddx,
                          int M, int C, uint32_t drop_thresh, float drop_scale, uint64_t seed, fer_stream_t stream);
 
+/* ---- LatentCNN2D (`latent_cnn.py:333-409`), csrc/conv2d.hip: the (18, 512) code as a one-channel image.
+ * Activations are pixel-major [M = B*H*W][C] (NHWC) in dtype, the 2-D form of [B*L][C]: BatchNorm2d
+ * (`:354,359,365`) is fer_batchnorm_fwd/_bwd with M = B*H*W, AdaptiveAvgPool2d(1) + Flatten (`:372,376`) is
+ * fer_seq_mean_fwd/_bwd with L = H*W. Same 16-byte piece rules as the LatentCNN baseline: C a multiple of 8
+ * (bf16) / 4 (fp32), row strides likewise, base pointers 16-byte aligned. No atomics, nothing stored for the
+ * backward; repeat calls are bit-identical. */
+
+/* im2col of nn.Conv2d(kernel_size=3, stride=1, padding=1) (`latent_cnn.py:358,364`):
+ *   cols[(b*H + h)*W + w][cin*9 + kh*3 + kw] = x[(b*H + h+kh-1)*W + (w+kw-1)][cin] inside the image, else 0
+ * (never the neighbouring row's or sample's pixel; values copied bit for bit). The (cin, kh, kw) column order
+ * is the memory order of nn.Conv2d.weight [Cout][Cin][3][3]: the parameter is fer_gemm's B operand with
+ * K = 9*Cin as it stands, and the weight gradient dy^T cols lands in the parameter's layout. x [M][C],
+ * cols [M][9*C]. */
+int fer_conv2d_cols(int dtype, const void* x, int64_t ldx, void* cols, int64_t ldc, int B, int H, int W, int C,
+                    fer_stream_t stream);
+/* Its adjoint: dx[m][c] = the sum over (kh, kw), in scan order, of dcols[m - (kh-1)*W - (kw-1)][c*9 + kh*3 + kw]
+ * over the output pixels inside the image (fp32 sum, rounded once). */
+int fer_conv2d_cols_bwd(int dtype, const void* dcols, int64_t ldd, void* dx, int64_t lddx, int B, int H, int W,
+                        int C, fer_stream_t stream);
+
+/* The first layer nn.Conv2d(1, Cout, kernel_size=3, padding=1) (`latent_cnn.py:353`), direct: x [M] scalars
+ * at element stride ldx (the model input (B, H, W) as it lies), w [Cout][9] and bias [Cout] (optional) fp32,
+ *   y[m][co] = bias[co] + sum_k x9[m][k] w[co][k],  x9[m][kh*3 + kw] = the pixel at (h+kh-1, w+kw-1) or 0,
+ * k in order, fmaf in fp32. Precision on the bf16 path: x is read as bf16, the weights and the bias are the
+ * fp32 parameters themselves (no bf16 shadow), the sum is fp32 and only y is rounded to bf16.
+ * Cout <= FER_CONV2D_C1_MAX_COUT (the weights sit in LDS). */
+#define FER_CONV2D_C1_MAX_COUT 1024
+int fer_conv2d_c1_fwd(int dtype, const void* x, int64_t ldx, const float* w, const float* bias, void* y, int64_t ldy,
+                      int B, int H, int W, int Cout, fer_stream_t stream);
+/* Backward. dw_part (optional, [n_parts][Cout*9] fp32, 16-byte aligned): row g = sum over the pixels m of
+ * strip g (ceil(M / n_parts) consecutive pixels) of dy[m][co] x9[m][k], in the parameter's layout; the caller
+ * adds the rows with fer_colsum (Cout*9 is a multiple of 4) and takes dbias from fer_colsum of dy. A strip
+ * without pixels is written as zeros. dx (optional, [M] scalars at stride lddx, needs w):
+ * dx[m] = sum_k sum_co dy[m - (kh-1)*W - (kw-1)][co] w[co][k] over the pixels inside the image. x is needed for
+ * dw_part only. Every sum is a fixed-order fp32 loop. */
+int fer_conv2d_c1_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* w,
+                      float* dw_part, int n_parts, void* dx, int64_t lddx, int B, int H, int W, int Cout,
+                      fer_stream_t stream);
+
+/* The stages behind BatchNorm2d + ReLU, nn.MaxPool2d((2, 2)) -> nn.Dropout2d (`latent_cnn.py:361-362,367-368`;
+ * pool = 0: Dropout2d alone, `:356`) in one launch. x [B*H*W][C] -> y [B*Ho*Wo][C], Ho = H / 2, Wo = W / 2
+ * (floor: a last odd row or column takes no part) with pool = 1, which needs H >= 2 and W >= 2; Ho = H, Wo = W
+ * with pool = 0. Dropout2d drops whole (sample, channel) planes: keep = the library's hash at element index
+ * b*C + c (u16 >= drop_thresh), y = keep ? max * drop_scale : exactly 0; drop_thresh = 0 (eval) passes the
+ * values bit for bit. The maximum is the window's first in (kh, kw) scan order under a strict > (PyTorch's
+ * tie rule). */
+int fer_pool2_chdrop_fwd(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int B, int H, int W, int C,
+                         int pool, uint32_t drop_thresh, float drop_scale, uint64_t seed, fer_stream_t stream);
+/* dx [B*H*W][C] = dy * keep * drop_scale at each window's argmax pixel, recomputed from the forward's x by
+ * the same rule, and exactly 0 elsewhere (the pixels floor division leaves out included). x is read with
+ * pool = 1 only. */
+int fer_pool2_chdrop_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, void* dx, int64_t lddx,
+                         int B, int H, int W, int C, int pool, uint32_t drop_thresh, float drop_scale, uint64_t seed,
+                         fer_stream_t stream);
+
 /* ---- AFS style extractor (`afs/style_extractor.py`), csrc/grouped.hip: G structurally identical blocks, one
  * launch per stage over all of them. Every operand of group g is `base + g * group_stride` (gs*, in
  * elements) with its own row stride (ld*), so a [B][G][K] tensor is one operand with ld = G*K, gs = K.

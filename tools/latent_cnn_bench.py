@@ -1,7 +1,7 @@
-"""Times the full LatentCNN ('standard', or 'deep' with --kind deep) train step of the HIP path against the identical torch.nn
+"""Times the full LatentCNN ('standard', or 'deep' / '2d' with --kind) train step of the HIP path against the identical torch.nn
 model in eager ROCm torch on the same GPU, interleaved (DESIGN.md "LatentCNN step time").
 
-    python tools/latent_cnn_bench.py [--kind standard|deep] [--batches 64 256] [--dtypes bf16 fp32] [--rounds 6] [--steps 20]
+    python tools/latent_cnn_bench.py [--kind standard|deep|2d] [--batches 64 256] [--dtypes bf16 fp32] [--rounds 6] [--steps 20]
     python tools/latent_cnn_bench.py --only native --batches 64 --dtypes bf16 --steps 30   # under a profiler
 
 Step = zero_grad, forward (dropout 0.3), CrossEntropyLoss, backward, AdamW (lr 1e-4, wd 1e-2), the
@@ -84,15 +84,32 @@ class TorchLatentCNNDeep(nn.Module):
         return self.head(torch.sum(x * self.attention(x), dim=2))
 
 
+class TorchLatentCNN2D(nn.Module):
+    """The (18, 512) code as a one-channel image: three Conv2d(3x3)-BN-ReLU stages (64, 128, 256) with
+    MaxPool2d((2, 2)) behind the last two and Dropout2d, global average pool, Linear-BN-ReLU-Dropout-Linear."""
+
+    def __init__(self, classes=7, p=0.3):
+        super().__init__()
+        self.features = nn.Sequential(
+            nn.Conv2d(1, 64, 3, padding=1), nn.BatchNorm2d(64), nn.ReLU(), nn.Dropout2d(p * 0.5),
+            nn.Conv2d(64, 128, 3, padding=1), nn.BatchNorm2d(128), nn.ReLU(), nn.MaxPool2d((2, 2)), nn.Dropout2d(p * 0.5),
+            nn.Conv2d(128, 256, 3, padding=1), nn.BatchNorm2d(256), nn.ReLU(), nn.MaxPool2d((2, 2)), nn.Dropout2d(p))
+        self.head = nn.Sequential(nn.Linear(256, 256), nn.BatchNorm1d(256), nn.ReLU(), nn.Dropout(p),
+                                  nn.Linear(256, classes))
+
+    def forward(self, x):
+        return self.head(self.features(x.unsqueeze(1)).mean((2, 3)))
+
+
 KIND = "standard"
 
 
 def native_step(dtype, x, y):
     from fervit.loss import CrossEntropyLoss
     from fervit.optim import FusedAdamW
-    from models_fer_vit.latent_cnn import create_latent_cnn
+    from models_fer_vit.latent_cnn import LatentCNN2D, create_latent_cnn
 
-    m = create_latent_cnn(KIND).cuda()
+    m = (LatentCNN2D() if KIND == "2d" else create_latent_cnn(KIND)).cuda()
     m.set_precision(dtype)
     m.train()
     opt = FusedAdamW(m.parameters(), lr=1e-4, weight_decay=1e-2, model=m)
@@ -109,7 +126,7 @@ def native_step(dtype, x, y):
 
 
 def torch_step(dtype, x, y):
-    m = (TorchLatentCNNDeep() if KIND == "deep" else TorchLatentCNN()).cuda()
+    m = {"deep": TorchLatentCNNDeep, "2d": TorchLatentCNN2D, "standard": TorchLatentCNN}[KIND]().cuda()
     m.train()
     opt = torch.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=1e-2)
     crit = nn.CrossEntropyLoss()
@@ -138,7 +155,7 @@ def block(step, steps):
 def main():
     global KIND
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", default="standard", choices=["standard", "deep"])
+    ap.add_argument("--kind", default="standard", choices=["standard", "deep", "2d"])
     ap.add_argument("--batches", type=int, nargs="+", default=[64, 256])
     ap.add_argument("--dtypes", nargs="+", default=["bf16", "fp32"], choices=["bf16", "fp32"])
     ap.add_argument("--rounds", type=int, default=6)
@@ -162,6 +179,12 @@ def main():
                     loss = s()
                 assert torch.isfinite(loss).item()
             torch.cuda.synchronize()
+            peak = None
+            if args.only:  # one arm alone in the process: its peak device memory over a step
+                torch.cuda.reset_peak_memory_stats()
+                steps[args.only]()
+                torch.cuda.synchronize()
+                peak = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
             ms = {k: [] for k in steps}
             for _ in range(1 if args.only else args.rounds):
                 for k, s in steps.items():
@@ -170,6 +193,8 @@ def main():
             for k, v in ms.items():
                 rec = {"arm": k, "model": f"latent_cnn {KIND}", "B": B, "dtype": dtype, "steps_per_block": args.steps,
                        "blocks": len(v), "median_ms_per_step": round(med[k], 4), "min_ms_per_step": round(min(v), 4)}
+                if peak is not None:
+                    rec["peak_allocated_MiB"] = peak
                 if k == "native" and "torch" in med:
                     rec["native_over_torch"] = round(med["native"] / med["torch"], 3)
                 print(json.dumps(rec), flush=True)
