@@ -513,7 +513,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ t, 
     s1 += gg;
     s2 += gg * xhat;
   }
-  if (tid < C) pp[(long)C * D + tid] = dlogits[(long)b * C + tid];
+  for (int c = tid; c < C; c += 256) pp[(long)C * D + c] = dlogits[(long)b * C + c];  // dbias, any C
   s1 = wave_sum(s1);
   s2 = wave_sum(s2);
   if (lane == 0) {
@@ -1278,6 +1278,7 @@ extern "C" int fer_wplus_bwd(const float* x, const float* saved, const float* dy
                              fer_stream_t stream) {
   (void)eps;
   if (B <= 0) return 0;
+  if (D > 1024) return set_error("wplus_bwd: D <= 1024");  // 4 x 256 columns per row, as the forward
   if (!ws || ws_bytes < fer_wplus_ws(B, L, D)) return set_error("wplus_bwd: workspace too small");
   const int nch = wplus_chunks(B);
   hipStream_t st = (hipStream_t)stream;

@@ -1,6 +1,6 @@
 """The harness the element-wise kernel tests share (tests/test_gpu_convbn.py, test_gpu_attnpool.py,
 test_gpu_rowops.py, test_gpu_gemm_elementwise.py, test_gpu_grouped_gemm.py, test_gpu_highway.py,
-test_gpu_attention_elementwise.py): access to the
+test_gpu_attention_elementwise.py, test_gpu_edge_kernels.py, test_gpu_optim_kernels.py): access to the
 C ABI, and operands as views into NaN-filled parents whose guard rows and padding columns must keep their
 bits. The bound arithmetic is tests/elemwise.py.
 
@@ -64,14 +64,15 @@ def _same_but(name, parent, inside):
 
 
 # ---------------------------------------------------------------------- [rows][cols] operands
-def nanview(rows, cols, pad, dt, src=None, guard=2):
+def nanview(rows, cols, pad, dt, src=None, guard=2, align=16):
     """[rows][cols] view inside a NaN-filled parent with `guard` rows above and below and `pad` extra
-    columns; returns (view, parent)."""
+    columns; returns (view, parent). `align`: the byte alignment the view's first element must have (a row
+    stride that is no multiple of 4 elements is only for kernels that move single elements)."""
     parent = torch.full((rows + 2 * guard, cols + pad), NAN, dtype=dt, device=DEV)
     v = parent[guard:guard + rows, :cols]
     if src is not None:
         v.copy_(src.to(dt))
-    assert v.data_ptr() % 16 == 0
+    assert v.data_ptr() % align == 0
     return v, parent
 
 
@@ -93,6 +94,21 @@ def nanvec(n):
 
 def untouched_vec(name, parent, n):
     _same_but(name + " guards", parent, slice(4, 4 + n))
+
+
+def nanflat(n, dt, src=None, guard=8, shift=0):
+    """[n] contiguous view of either dtype inside a NaN-filled parent, `guard` elements in front (16-byte
+    aligned for guard = 8; `shift` more elements move it off that alignment) and at least as many behind;
+    returns (view, parent)."""
+    parent = torch.full((n + 2 * guard + shift,), NAN, dtype=dt, device=DEV)
+    v = parent[guard + shift:guard + shift + n]
+    if src is not None:
+        v.copy_(src.reshape(-1).to(dt))
+    return v, parent
+
+
+def untouched_flat(name, parent, n, guard=8, shift=0):
+    _same_but(name + " guards", parent, slice(guard + shift, guard + shift + n))
 
 
 # ---------------------------------------------------------------------- grouped [G][rows][cols] operands

@@ -56,3 +56,34 @@ def keep_mask_torch(seed: int, shape, p: float, device="cuda") -> torch.Tensor:
     x ^= x >> 16
     u = (x >> ((idx & 1) * 16)) & 0xFFFF
     return (u >= thresh(p)).reshape(shape)
+
+
+# ---------------------------------------------------------------------- latent augmentation draws
+# csrc/misc.hip latent_augment_kernel: three streams keyed by sub-seeds of the call's seed (step counter
+# unset), each a fer_hash of a 32-bit counter mapped to (0, 1] by u01.
+SCALE_XOR = 0x5851F42D4C957F2D
+MASK_XOR = 0x14057B7EF767814F
+
+
+def sub_seeds(seed: int):
+    """(noise, scale, mask) seeds of fer_latent_augment."""
+    return seed, seed ^ SCALE_XOR, seed ^ MASK_XOR
+
+
+def u01(h: np.ndarray) -> np.ndarray:
+    """csrc/misc.hip u01 in the kernel's own float32 arithmetic: ((float)(h >> 8) + 0.5f) * 2^-24. The sum
+    is rounded to float32 (to even above 2^23), so the top value is 1.0 and the bottom one 2^-25."""
+    k = (_u32(h) >> np.uint64(8)).astype(np.float32)
+    return (k + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+
+
+def augment_draws(seed: int, n: int, B: int):
+    """float32 (u1, u2) of the Box-Muller noise and the mask uniform of elements 0..n-1, and the scale
+    uniform of samples 0..B-1."""
+    s_noise, s_scale, s_mask = sub_seeds(seed)
+    e = np.arange(n, dtype=np.uint64)
+    u1 = u01(fer_hash(s_noise, 2 * e))
+    u2 = u01(fer_hash(s_noise, 2 * e + 1))
+    um = u01(fer_hash(s_mask, e))
+    us = u01(fer_hash(s_scale, np.arange(B, dtype=np.uint64)))
+    return u1, u2, um, us
