@@ -59,6 +59,46 @@ extern "C" int fer_gemm(const fer_gemm_desc* d, const fer_epilogue* e, fer_strea
   return fer::gemm_launch(*d, *e, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- evaluation metrics (kernels: metrics.hip)
+extern "C" int fer_cls_stats(const float* logits, int64_t ld, const int64_t* labels, int B, int C, int64_t* preds,
+                             float* conf, float* probs, int64_t ld_probs, int64_t* confusion, int64_t* counters,
+                             fer_stream_t stream) {
+  if (C < 1) return fer::set_error("cls_stats: C must be >= 1");
+  if (!logits || !labels) return fer::set_error("cls_stats: logits and labels are required");
+  if (ld < C) return fer::set_error("cls_stats: the logits' row stride must be >= C");
+  if (probs && ld_probs < C) return fer::set_error("cls_stats: the probabilities' row stride must be >= C");
+  if (B <= 0) return 0;
+  if (fer::too_many((long)B * 64)) return fer::set_error("cls_stats: B is too large for one launch");
+  fer::cls_stats_launch(logits, ld, labels, B, C, preds, conf, probs, ld_probs, confusion, counters, (hipStream_t)stream);
+  return fer::hip_check("cls_stats");
+}
+
+extern "C" int fer_cls_report(const int64_t* confusion, int C, double* out, fer_stream_t stream) {
+  if (C < 1) return fer::set_error("cls_report: C must be >= 1");
+  if (!confusion || !out) return fer::set_error("cls_report: confusion and out are required");
+  fer::cls_report_launch(confusion, C, out, (hipStream_t)stream);
+  return fer::hip_check("cls_report");
+}
+
+extern "C" int fer_token_cosine(int dtype, const void* tokens, int64_t ld, int B, int N, int D, float eps,
+                                float* cls_sim, int64_t ld_cls, float* tok_sim, int64_t ld_tok, fer_stream_t stream) {
+  if (fer::check_dtype(dtype, "token_cosine: unknown dtype")) return -1;
+  if (N < 2) return fer::set_error("token_cosine: N must be >= 2 (row 0 and at least one more token)");
+  const int V = fer::piece_len(dtype);
+  if (D < 1 || D % (dtype == FER_BF16 ? 32 : 4))
+    return fer::set_error("token_cosine: D must be a positive multiple of 32 (bf16: one MFMA step) or 4 (fp32)");
+  if (!fer::piece_ok(tokens, ld, D, V))
+    return fer::set_error("token_cosine: tokens need 16-byte aligned rows (stride >= D, a multiple of 8 bf16 / 4 fp32)");
+  if (!cls_sim && !tok_sim) return fer::set_error("token_cosine: no output requested");
+  if ((cls_sim && ld_cls < N - 1) || (tok_sim && ld_tok < N - 1))
+    return fer::set_error("token_cosine: an output's row stride must be >= N - 1");
+  if (!(eps >= 0.f)) return fer::set_error("token_cosine: eps must be >= 0");
+  if (B <= 0) return 0;
+  if (B > 65535 || N > 65535) return fer::set_error("token_cosine: B or N is above the launch grid's limit");
+  fer::token_cosine_launch(dtype, tokens, ld, B, N, D, eps, cls_sim, ld_cls, tok_sim, ld_tok, (hipStream_t)stream);
+  return fer::hip_check("token_cosine");
+}
+
 extern "C" int fer_set_step_counter(const uint64_t* counter) {
   // every code object that has dropout kernels keeps its own copy of the pointer
   if (fer::set_step_ptr_gemm(counter) || fer::set_step_ptr_attention(counter) ||

@@ -40,6 +40,12 @@ bool fixed_stride_mode();
 // compute units of the current device (256 when the query fails), asked once per process
 int num_cus();
 int gemm_launch(const GemmDesc& d, const EpiArgs& e, hipStream_t st);
+// evaluation metrics (metrics.hip): launches only, the entry points in capi.cpp check the arguments
+void cls_stats_launch(const float* logits, long ld, const int64_t* labels, int B, int C, int64_t* preds, float* conf,
+                      float* probs, long ld_probs, int64_t* confusion, int64_t* counters, hipStream_t st);
+void cls_report_launch(const int64_t* confusion, int C, double* out, hipStream_t st);
+void token_cosine_launch(int dtype, const void* tokens, long ld, int B, int N, int D, float eps, float* cls_sim,
+                         long ld_cls, float* tok_sim, long ld_tok, hipStream_t st);
 inline int ceil_div(long a, long b);
 // out_k[c % seg] (+)= scale * sum_b part[b*ld + c]  (deterministic, misc.hip)
 void part_reduce(const float* part, int nb, long ld, int ncols, int seg, float* o0, float* o1, float* o2,

@@ -10,11 +10,19 @@ the per-head [B, H, N, N] tensor is only written when asked for.
     maps = attention_maps(model, x)              # [L, B, N, N], mean over heads
     r    = attention_rollout(model, x)           # [B, N], CLS row of the rollout
     sal  = cls_saliency(model, x)                # [B, gh, gw] (patch models) / [B, tokens] (w+ models)
+    t    = final_tokens(model, x)                # [B, N, D], what the head's LayerNorm reads
+    cls_sim, tok_sim = token_similarity(model, x)  # [B, N-1], [B, N-1, N-1]
 
 Maps are an eval / no-grad feature: a tapped forward that records gradients, has attention
 dropout on or runs under graph capture raises RuntimeError. The tap sits in the layer functions,
 so every model built from them (ImageViT, LatentViT, LatentViTv2, HybridLatentViT with or
 without adapters, ExpressionAwareViT) is covered by the same code.
+
+The reference's `eval/evaluate_model.py:231-296` (visualize_attention) re-runs the model's parts by hand to
+reach the encoder output, then takes the cosine similarity of the final CLS token with every other token
+and of those tokens with each other. The fused models go from tokens straight to logits (HeadFn), so
+fervit.layers.TOKEN_TAP hands the final tokens out, under the same eval / no-grad / no-capture rule, and
+fer_token_cosine computes both similarities in one launch.
 """
 from __future__ import annotations
 
@@ -97,6 +105,36 @@ def cls_saliency(model, x, residual: float = 0.5) -> torch.Tensor:
                 return r
         return r.reshape(r.shape[0], gh, gw)
     return r
+
+
+def final_tokens(model, x) -> torch.Tensor:
+    """[B, N, D]: the encoder output the model's head reads (row 0 of each batch element is the CLS token),
+    in the model's compute dtype, from one eval forward under torch.no_grad(). The model's train / eval
+    mode and the previous tap are restored."""
+    got: List[torch.Tensor] = []
+
+    def tap(t, cfg):
+        got.append(t.view(cfg.B, cfg.N, t.shape[1]))
+
+    was_training = model.training
+    prev = _layers.TOKEN_TAP
+    model.eval()
+    _layers.TOKEN_TAP = tap
+    try:
+        with torch.no_grad():
+            model(x)
+    finally:
+        _layers.TOKEN_TAP = prev
+        model.train(was_training)
+    if len(got) != 1:
+        raise RuntimeError(f"fervit: the model ran {len(got)} fused heads (HeadFn), expected 1")
+    return got[0]
+
+
+def token_similarity(model, x, eps: float = 1e-8):
+    """(cls_sim [B, N-1], tok_sim [B, N-1, N-1]), fp32: cosine similarity of the final CLS token with every
+    other final token, and of those tokens with each other (torch.cosine_similarity's definition)."""
+    return ops.token_cosine(final_tokens(model, x), eps)
 
 
 def rollout_reference(maps: torch.Tensor, residual: float = 0.5) -> torch.Tensor:

@@ -55,6 +55,20 @@ def _attn_tap(qkv: torch.Tensor, cfg: LayerCfg) -> None:
     ATTN_TAP(qkv, cfg)
 
 
+# Optional callable(t, cfg) run by HeadFn.forward on the final tokens t [B*N, D], before the head reads
+# its CLS rows (fervit.explain installs it for final_tokens / token_similarity). Same rule as ATTN_TAP.
+TOKEN_TAP = None
+
+
+def _token_tap(t: torch.Tensor, cfg: LayerCfg) -> None:
+    if cfg.save or cfg.dropout > 0 or torch.cuda.is_current_stream_capturing():
+        why = ("gradients are being recorded" if cfg.save else
+               "head dropout is on" if cfg.dropout > 0 else "the stream is being captured")
+        raise RuntimeError(f"fervit: the final tokens are an eval / no-grad feature ({why}): call model.eval() and "
+                           "run the forward under torch.no_grad(), outside graph capture")
+    TOKEN_TAP(t, cfg)
+
+
 def _weight(flat: FlatParams, p: torch.nn.Parameter, dt: torch.dtype) -> torch.Tensor:
     """Matrix operand in the compute dtype (bf16 shadow or the fp32 master)."""
     return flat.half_view(p) if dt == torch.bfloat16 else p.data
@@ -501,6 +515,8 @@ class HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, cfg: LayerCfg, flat: FlatParams, *P):
         lnw, lnb, W, b = P
+        if TOKEN_TAP is not None:
+            _token_tap(t, cfg)
         seed = next_seed() if cfg.dropout > 0 else 0
         logits, stats = ops.head_fwd(t, cfg.N, lnw.data, lnb.data, cfg.eps, W.data, b.data, cfg.B,
                                      dropout=cfg.dropout, seed=seed)

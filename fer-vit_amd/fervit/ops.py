@@ -314,6 +314,78 @@ def attention_rollout_cls(maps, residual=0.5, out=None):
     return out
 
 
+# ------------------------------------------------------------------ evaluation metrics
+def _out(name, t, like, shape, dtype):
+    """An optional caller-given output: `dtype`, `shape`, unit last stride, on like's device."""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != like.device or \
+            (t.dim() and t.shape[-1] > 1 and t.stride(-1) != 1):
+        raise ValueError(f"{name} must be a {dtype} {tuple(shape)} tensor with unit last stride on the input's device")
+    return t
+
+
+def cls_stats(logits, labels, *, confusion=None, counters=None, want_preds=True, want_conf=True, want_probs=False):
+    """One fer_cls_stats launch on fp32 logits [B, C] (unit column stride) and int64 labels [B]: returns
+    (preds int64 [B], conf fp32 [B], probs fp32 [B, C]), None for what was not asked for. `confusion`
+    (int64 [C, C], contiguous) and `counters` (int64 [2]: rows counted, rows skipped) are accumulated in
+    place; a label outside [0, C) is skipped. No host sync: usable under graph capture."""
+    _dev(logits)
+    _dev(labels)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[1] < 1 or \
+            (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError("cls_stats: logits must be fp32 [B, C >= 1] with unit column stride")
+    B, C = logits.shape
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or (B > 1 and labels.stride(0) != 1):
+        raise ValueError("cls_stats: labels must be a contiguous int64 [B] tensor")
+    if confusion is not None and not _out("cls_stats: confusion", confusion, logits, (C, C), torch.int64).is_contiguous():
+        raise ValueError("cls_stats: confusion must be contiguous")
+    if counters is not None:
+        _out("cls_stats: counters", counters, logits, (2,), torch.int64)
+    preds = torch.empty(B, dtype=torch.int64, device=logits.device) if want_preds else None
+    conf = torch.empty(B, dtype=torch.float32, device=logits.device) if want_conf else None
+    probs = torch.empty(B, C, dtype=torch.float32, device=logits.device) if want_probs else None
+    if B == 0:
+        return preds, conf, probs
+    check(lib().fer_cls_stats(logits.data_ptr(), logits.stride(0) if B > 1 else max(C, logits.stride(0)),
+                              labels.data_ptr(), B, C, ptr(preds), ptr(conf), ptr(probs), C, ptr(confusion),
+                              ptr(counters), stream()), "cls_stats")
+    return preds, conf, probs
+
+
+def cls_report(confusion, out=None):
+    """fer_cls_report of a contiguous int64 [C, C] confusion matrix: fp64 [4 + 4 C] on the device
+    (accuracy, f1_macro, f1_weighted, n, then precision, recall, f1, support per class)."""
+    _dev(confusion)
+    if confusion.dtype != torch.int64 or confusion.dim() != 2 or confusion.shape[0] != confusion.shape[1] \
+            or confusion.shape[0] < 1 or not confusion.is_contiguous():
+        raise ValueError("cls_report: confusion must be a contiguous int64 [C, C] tensor, C >= 1")
+    C = confusion.shape[0]
+    if out is None:
+        out = torch.empty(4 + 4 * C, dtype=torch.float64, device=confusion.device)
+    elif not _out("cls_report: out", out, confusion, (4 + 4 * C,), torch.float64).is_contiguous():
+        raise ValueError("cls_report: out must be contiguous")
+    check(lib().fer_cls_report(confusion.data_ptr(), C, out.data_ptr(), stream()), "cls_report")
+    return out
+
+
+def token_cosine(tokens, eps=1e-8, want_cls=True, want_tok=True):
+    """fer_token_cosine of tokens [B, N, D] (bf16 or fp32; unit column stride, batch stride N * row
+    stride): (cls_sim fp32 [B, N-1], tok_sim fp32 [B, N-1, N-1]), None for what was not asked for."""
+    _dev(tokens)
+    code = dcode(tokens)
+    if tokens.dim() != 3 or tokens.shape[1] < 2 or tokens.shape[2] < 1:
+        raise ValueError("token_cosine: tokens must be [B, N >= 2, D]")
+    B, N, D = tokens.shape
+    if tokens.stride(2) != 1 or tokens.stride(1) < D or (B > 1 and tokens.stride(0) != N * tokens.stride(1)):
+        raise ValueError("token_cosine: tokens need unit column stride and a batch stride of N rows")
+    if not (want_cls or want_tok):
+        raise ValueError("token_cosine: no output requested")
+    cls = torch.empty(B, N - 1, dtype=torch.float32, device=tokens.device) if want_cls else None
+    tok = torch.empty(B, N - 1, N - 1, dtype=torch.float32, device=tokens.device) if want_tok else None
+    check(lib().fer_token_cosine(code, tokens.data_ptr(), tokens.stride(1), B, N, D, float(eps), ptr(cls), N - 1,
+                                 ptr(tok), N - 1, stream()), "token_cosine")
+    return cls, tok
+
+
 # ------------------------------------------------------------------ misc
 def colsum(x, out, accumulate=False, scale=None):
     M, N = x.shape

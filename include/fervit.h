@@ -200,6 +200,41 @@ int fer_attention_probs(int dtype, const void* qkv, int64_t ld_qkv, int B, int N
  * 1 <= N <= 7680 (r is double-buffered in LDS); residual outside [0, 1) is an error. */
 int fer_attention_rollout_cls(const float* maps, int L, int B, int N, float residual, float* r, fer_stream_t stream);
 
+/* Evaluation metrics (`eval/evaluate_model.py:135-159`: softmax, argmax and the host's sklearn
+ * confusion_matrix / classification_report; `eval/evaluate_model.py:231-296`: cosine similarity of the
+ * final tokens). One kernel per call, no host read, no allocation: each call can be captured.
+ *
+ * fer_cls_stats: one batch of fp32 logits [B][C] (row stride ld) and int64 labels [B]. Outputs, each
+ * optional (NULL skips it):
+ *   preds int64 [B]       lowest index of the row maximum; a NaN counts as the maximum and the first NaN
+ *                         wins (torch.argmax's CPU rule: [1, 5, 5, 2] -> 1, [1, nan, 5, nan] -> 1)
+ *   probs fp32 [B][C]     exp(z_i - m) / sum_j exp(z_j - m), m the row maximum, fp32, the sum in one fixed
+ *                         order (row stride ld_probs)
+ *   conf fp32 [B]         probs[pred]
+ *   confusion int64 [C][C], contiguous, row = label, column = prediction: ACCUMULATED (64-bit atomic adds;
+ *                         integer adds give the same bits in any order); the caller zeroes it once per epoch
+ *   counters int64 [2]    rows counted, rows skipped: accumulated too
+ * A label outside [0, C) (-100, -1, C) adds nothing to confusion and one to the skipped counter; preds,
+ * conf and probs of that row are still written. C < 1, ld < C, ld_probs < C, NULL logits or labels: a
+ * negative code, a message, nothing launched. B <= 0 is a no-op.
+ *
+ * fer_cls_report: confusion [C][C] -> out fp64 [4 + 4*C]: accuracy, f1_macro, f1_weighted, n, then per
+ * class precision, recall, f1, support. One workgroup, fp64, fixed order. A zero denominator gives 0
+ * (sklearn's zero_division default); f1_macro averages over the classes present in labels or predictions
+ * (row sum + column sum > 0: sklearn's rule for labels=None); n = 0 gives all zeros.
+ *
+ * fer_token_cosine: tokens [B][N][D] (bf16 or fp32; row stride ld, batch stride N*ld), cos(x, y) =
+ * x.y / (max(|x|, eps) * max(|y|, eps)) (torch.cosine_similarity's per-vector clamp). cls_sim fp32
+ * [B][N-1] (row stride ld_cls): row 0 against rows 1..N-1; tok_sim fp32 [B][N-1][N-1] (row stride ld_tok,
+ * batch stride (N-1)*ld_tok): rows 1..N-1 against each other. Each optional, at least one required; alone
+ * or together they hold the same bits. bf16: MFMA Gram tiles, D % 32 == 0, ld % 8 == 0; fp32: FMA,
+ * D % 4 == 0, ld % 4 == 0; tokens 16-byte aligned; N >= 2. Squared norms in fp32. */
+int fer_cls_stats(const float* logits, int64_t ld, const int64_t* labels, int B, int C, int64_t* preds, float* conf,
+                  float* probs, int64_t ld_probs, int64_t* confusion, int64_t* counters, fer_stream_t stream);
+int fer_cls_report(const int64_t* confusion, int C, double* out, fer_stream_t stream);
+int fer_token_cosine(int dtype, const void* tokens, int64_t ld, int B, int N, int D, float eps, float* cls_sim,
+                     int64_t ld_cls, float* tok_sim, int64_t ld_tok, fer_stream_t stream);
+
 /* Column sums: out[n] (+)= scale * sum_m x[m][n]  (bias gradients). ws >= fer_colsum_ws(M,N). */
 int64_t fer_colsum_ws(int M, int N);
 int fer_colsum(int dtype, const void* x, int64_t ldx, int M, int N, float* out, int accumulate,
