@@ -99,6 +99,54 @@ extern "C" int fer_token_cosine(int dtype, const void* tokens, int64_t ld, int B
   return fer::hip_check("token_cosine");
 }
 
+// ---------------------------------------------------------------- linear-SVM passes (kernels: svm.hip)
+extern "C" int fer_svm_slab(void) { return FER_SVM_SLAB; }
+extern "C" int fer_svm_max_groups(void) { return FER_SVM_MAX_GROUPS; }
+extern "C" int64_t fer_svm_ws(int N, int F) { return N > 0 && F > 0 ? fer::svm_ws_bytes(N, F) : 0; }
+
+// what both passes ask of X, the shape and the workspace; `what` is the entry's name
+static int svm_common(const char* what, const float* X, int64_t ldx, int N, int F, int P, const float* ws,
+                      int64_t ws_bytes) {
+  char msg[160];
+  const char* bad = nullptr;
+  if (F < 1) bad = "F must be >= 1";
+  else if (P < 1 || P > 8) bad = "P must be 1..8 columns per launch";
+  else if (!X || ldx < F) bad = "X is required, with a row stride >= F";
+  else if (N > 0 && (!ws || !fer::al16(ws) || ws_bytes < fer::svm_ws_bytes(N, F)))
+    bad = "the workspace must be 16-byte aligned and hold fer_svm_ws(N, F) bytes";
+  if (!bad) return 0;
+  snprintf(msg, sizeof(msg), "%s: %s", what, bad);
+  return fer::set_error(msg);
+}
+
+extern "C" int fer_svm_forward(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, int N,
+                               int F, int P, int epilogue, const int64_t* labels, const int64_t* classes,
+                               const float* Cp, const float* Cn, float* Z, int64_t ldz, float* R, int64_t ldr,
+                               float* Dw, int64_t ldd, float* loss, float* ws, int64_t ws_bytes, fer_stream_t stream) {
+  if (svm_common("svm_forward", X, ldx, N, F, P, ws, ws_bytes)) return -1;
+  if (epilogue != 0 && epilogue != 1) return fer::set_error("svm_forward: epilogue must be 0 (hinge) or 1 (scale)");
+  if (!W || ldw < F || !bias) return fer::set_error("svm_forward: W (row stride >= F) and bias are required");
+  if (!R || ldr < P || !Dw || ldd < P) return fer::set_error("svm_forward: R and Dw are required, with row strides >= P");
+  if (Z && ldz < P) return fer::set_error("svm_forward: Z's row stride must be >= P");
+  if (epilogue == 0 && (!labels || !classes || !Cp || !Cn || !loss))
+    return fer::set_error("svm_forward: the hinge epilogue needs labels, classes, Cp, Cn and loss");
+  if (N <= 0) return 0;
+  fer::svm_forward_launch(X, ldx, W, ldw, bias, N, F, P, epilogue == 0, labels, classes, Cp, Cn, Z, ldz, R, ldr, Dw, ldd,
+                          loss, ws, (hipStream_t)stream);
+  return fer::hip_check("svm_forward");
+}
+
+extern "C" int fer_svm_xtr(const float* X, int64_t ldx, const float* R, int64_t ldr, int N, int F, int P, float* G,
+                           int64_t ldg, float* gb, float* ws, int64_t ws_bytes, fer_stream_t stream) {
+  if (svm_common("svm_xtr", X, ldx, N, F, P, ws, ws_bytes)) return -1;
+  if (!R || ldr < P) return fer::set_error("svm_xtr: R is required, with a row stride >= P");
+  if (!G && !gb) return fer::set_error("svm_xtr: no output requested");
+  if (G && ldg < F) return fer::set_error("svm_xtr: G's row stride must be >= F");
+  if (N <= 0) return 0;
+  fer::svm_xtr_launch(X, ldx, R, ldr, N, F, P, G, ldg, gb, ws, (hipStream_t)stream);
+  return fer::hip_check("svm_xtr");
+}
+
 extern "C" int fer_set_step_counter(const uint64_t* counter) {
   // every code object that has dropout kernels keeps its own copy of the pointer
   if (fer::set_step_ptr_gemm(counter) || fer::set_step_ptr_attention(counter) ||

@@ -46,6 +46,14 @@ void cls_stats_launch(const float* logits, long ld, const int64_t* labels, int B
 void cls_report_launch(const int64_t* confusion, int C, double* out, hipStream_t st);
 void token_cosine_launch(int dtype, const void* tokens, long ld, int B, int N, int D, float eps, float* cls_sim,
                          long ld_cls, float* tok_sim, long ld_tok, hipStream_t st);
+// linear-SVM passes (svm.hip): launches only, the entry points in capi.cpp check the arguments
+long svm_ws_bytes(int N, int F);
+void svm_forward_launch(const float* X, long ldx, const float* W, long ldw, const float* bias, int N, int F, int P,
+                        int hinge, const int64_t* labels, const int64_t* classes, const float* Cp, const float* Cn,
+                        float* Z, long ldz, float* R, long ldr, float* Dw, long ldd, float* loss, float* ws,
+                        hipStream_t st);
+void svm_xtr_launch(const float* X, long ldx, const float* R, long ldr, int N, int F, int P, float* G, long ldg,
+                    float* gb, float* ws, hipStream_t st);
 inline int ceil_div(long a, long b);
 // out_k[c % seg] (+)= scale * sum_b part[b*ld + c]  (deterministic, misc.hip)
 void part_reduce(const float* part, int nb, long ld, int ncols, int seg, float* o0, float* o1, float* o2,

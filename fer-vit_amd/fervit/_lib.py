@@ -73,6 +73,12 @@ SIGNATURES = {
     "fer_cls_stats": (i32, [fp, i64, vp, i32, i32, vp, fp, fp, i64, vp, vp, vp]),
     "fer_cls_report": (i32, [vp, i32, vp, vp]),
     "fer_token_cosine": (i32, [i32, vp, i64, i32, i32, i32, f32, fp, i64, fp, i64, vp]),
+    "fer_svm_slab": (i32, []),
+    "fer_svm_max_groups": (i32, []),
+    "fer_svm_ws": (i64, [i32, i32]),
+    "fer_svm_forward": (i32, [fp, i64, fp, i64, fp, i32, i32, i32, i32, vp, vp, fp, fp, fp, i64, fp, i64, fp, i64, fp,
+                              fp, i64, vp]),
+    "fer_svm_xtr": (i32, [fp, i64, fp, i64, i32, i32, i32, fp, i64, fp, fp, i64, vp]),
     "fer_colsum_ws": (i64, [i32, i32]),
     "fer_colsum": (i32, [i32, vp, i64, i32, i32, fp, i32, fp, fp, i64, vp]),
     "fer_reduce_defer": (i32, [i32, vp, i64, vp]),

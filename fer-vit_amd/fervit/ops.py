@@ -386,6 +386,91 @@ def token_cosine(tokens, eps=1e-8, want_cls=True, want_tok=True):
     return cls, tok
 
 
+# ------------------------------------------------------------------ linear-SVM passes
+SVM_COLUMNS = 8  # columns (one-vs-rest problems) per launch
+
+
+def svm_slab() -> int:
+    """Rows per slab of fer_svm_xtr's fixed summation order."""
+    return lib().fer_svm_slab()
+
+
+def _svm_x(X, what):
+    _dev(X)
+    if X.dtype != torch.float32 or X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1 or \
+            (X.shape[1] > 1 and X.stride(1) != 1) or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
+        raise ValueError(f"{what}: X must be fp32 [N >= 1, F >= 1] with unit column stride")
+    N, F = X.shape
+    return N, F, (X.stride(0) if N > 1 else max(F, X.stride(0)))
+
+
+def _svm_cols(name, t, like, rows, P, dtype=torch.float32):
+    """A contiguous [rows, P] (or [P] for rows = None) operand on like's device."""
+    shape = (P,) if rows is None else (rows, P)
+    if t.dtype != dtype or tuple(t.shape) != shape or t.device != like.device or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on X's device")
+    return t
+
+
+def _svm_forward(X, W, bias, epilogue, labels, classes, Cp, Cn, Dw, want_z):
+    what = "svm_hinge" if epilogue == 0 else "svm_scale"
+    N, F, ldx = _svm_x(X, what)
+    if W.dim() != 2 or not 1 <= W.shape[0] <= SVM_COLUMNS:
+        raise ValueError(f"{what}: W must be [P, F] with 1 <= P <= {SVM_COLUMNS}")
+    P = W.shape[0]
+    _svm_cols(f"{what}: W", W, X, P, F)
+    _svm_cols(f"{what}: bias", bias, X, None, P)
+    R = torch.empty(N, P, dtype=torch.float32, device=X.device)
+    Z = torch.empty(N, P, dtype=torch.float32, device=X.device) if want_z else None
+    loss = None
+    if epilogue == 0:
+        _svm_cols(f"{what}: labels", labels, X, None, N, torch.int64)
+        _svm_cols(f"{what}: classes", classes, X, None, P, torch.int64)
+        _svm_cols(f"{what}: Cp", Cp, X, None, P)
+        _svm_cols(f"{what}: Cn", Cn, X, None, P)
+        Dw = torch.empty(N, P, dtype=torch.float32, device=X.device)
+        loss = torch.empty(P, dtype=torch.float32, device=X.device)
+    else:
+        _svm_cols(f"{what}: Dw", Dw, X, N, P)
+    check(lib().fer_svm_forward(X.data_ptr(), ldx, W.data_ptr(), F, bias.data_ptr(), N, F, P, epilogue, ptr(labels),
+                                ptr(classes), ptr(Cp), ptr(Cn), ptr(Z), P, R.data_ptr(), P, Dw.data_ptr(), P, ptr(loss),
+                                *_ws(lib().fer_svm_ws(N, F), X.device), stream()), what)
+    return R, Dw, loss, Z
+
+
+def svm_hinge(X, W, bias, labels, classes, Cp, Cn, want_z=False):
+    """fer_svm_forward with the hinge epilogue on X fp32 [N, F], W [P, F], bias [P], labels int64 [N], classes
+    int64 [P], Cp, Cn [P]: (R [N, P] residual c a s m, Dw [N, P] curvature weights c a, loss [P] = sum c a m^2,
+    Z [N, P] = X W^T + bias or None)."""
+    return _svm_forward(X, W, bias, 0, labels, classes, Cp, Cn, None, want_z)
+
+
+def svm_scale(X, V, vbias, Dw):
+    """fer_svm_forward with the scale epilogue: Dw * (X V^T + vbias) [N, P], the inner half of a Hessian-vector
+    product."""
+    return _svm_forward(X, V, vbias, 1, None, None, None, None, Dw, False)[0]
+
+
+def svm_decision(X, W, bias):
+    """Z = X W^T + bias [N, P] alone (the scale epilogue with zero weights; its product is dropped)."""
+    Dw = torch.zeros(X.shape[0], W.shape[0], dtype=torch.float32, device=X.device)
+    return _svm_forward(X, W, bias, 1, None, None, None, None, Dw, True)[3]
+
+
+def svm_xtr(X, R):
+    """fer_svm_xtr: (G [P, F] = R^T X, gb [P] = column sums of R), in the fixed slab order."""
+    N, F, ldx = _svm_x(X, "svm_xtr")
+    if R.dim() != 2 or not 1 <= R.shape[1] <= SVM_COLUMNS:
+        raise ValueError(f"svm_xtr: R must be [N, P] with 1 <= P <= {SVM_COLUMNS}")
+    P = R.shape[1]
+    _svm_cols("svm_xtr: R", R, X, N, P)
+    G = torch.empty(P, F, dtype=torch.float32, device=X.device)
+    gb = torch.empty(P, dtype=torch.float32, device=X.device)
+    check(lib().fer_svm_xtr(X.data_ptr(), ldx, R.data_ptr(), P, N, F, P, G.data_ptr(), F, gb.data_ptr(),
+                            *_ws(lib().fer_svm_ws(N, F), X.device), stream()), "svm_xtr")
+    return G, gb
+
+
 # ------------------------------------------------------------------ misc
 def colsum(x, out, accumulate=False, scale=None):
     M, N = x.shape

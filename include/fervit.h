@@ -235,6 +235,41 @@ int fer_cls_report(const int64_t* confusion, int C, double* out, fer_stream_t st
 int fer_token_cosine(int dtype, const void* tokens, int64_t ld, int B, int N, int D, float eps, float* cls_sim,
                      int64_t ld_cls, float* tok_sim, int64_t ld_tok, fer_stream_t stream);
 
+/* Batched linear-SVM passes (`latent_analysis/compute_expression_direction.py:58-116`: LinearSVC(C = 0.1,
+ * class_weight = 'balanced') on the flattened w+ latents; fervit/directions.py holds the solver). Column p of a
+ * launch is the one-vs-rest problem of class classes[p]:
+ *   f_p(w, b) = 1/2 |w|^2 + 1/2 b^2 + sum_i c_i max(0, m_i)^2,  m_i = 1 - s_i (w.x_i + b),
+ *   s_i = +1 if labels[i] == classes[p] else -1,  c_i = Cp[p] for s_i = +1, Cn[p] for s_i = -1
+ * (liblinear's L2-regularised squared hinge with a regularised bias). All fp32, fp32 accumulation, 1 <= P <= 8
+ * columns per launch, every row stride an argument (in floats, >= the row length; rows need no alignment: a
+ * 16-byte aligned operand with a stride that is a multiple of 4 moves in 16-byte pieces, any other element by
+ * element, with the same bits). No host read, no allocation: capturable. ws: 16-byte aligned,
+ * >= fer_svm_ws(N, F) bytes. Every sum has a fixed partition and order (no floating-point atomics): the same
+ * input gives the same bits on every call.
+ *
+ * fer_svm_forward: Z[N][P] = X[N][F] W[P][F]^T + bias[P] (Z optional), then
+ *   epilogue 0 (hinge): labels int64 [N], classes int64 [P], Cp, Cn fp32 [P] -> R[i][p] = c a s m (the
+ *     residual: grad_w f_p = w - 2 sum_i R[i][p] x_i, d f_p / d b = b - 2 sum_i R[i][p]), Dw[i][p] = c a with
+ *     a = [m > 0] (the curvature weights: the Hessian is I + 2 X^T diag(Dw) X, bias column included), and
+ *     loss[p] = sum_i c a m^2, summed per 256 rows and then over those sums in row order;
+ *   epilogue 1 (scale): Dw is read, R[i][p] = Dw[i][p] Z[i][p]: the inner half of a Hessian-vector product
+ *     (W holds the direction, bias its bias component).
+ * fer_svm_xtr: G[P][F] = sum_i R[i][p] X[i][f], gb[P] = sum_i R[i][p] (each optional, one required). Rows are
+ * cut into slabs of FER_SVM_SLAB; a sum runs over a slab's rows in order, over the slabs of a group in order
+ * (ceil(slabs / FER_SVM_MAX_GROUPS) consecutive slabs per group), then over the groups in order.
+ * N <= 0 is a no-op; a bad argument returns a negative code and a message and launches nothing. */
+#define FER_SVM_SLAB 32
+#define FER_SVM_MAX_GROUPS 128
+int fer_svm_slab(void);
+int fer_svm_max_groups(void);
+int64_t fer_svm_ws(int N, int F);
+int fer_svm_forward(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, int N, int F, int P,
+                    int epilogue, const int64_t* labels, const int64_t* classes, const float* Cp, const float* Cn,
+                    float* Z, int64_t ldz, float* R, int64_t ldr, float* Dw, int64_t ldd, float* loss, float* ws,
+                    int64_t ws_bytes, fer_stream_t stream);
+int fer_svm_xtr(const float* X, int64_t ldx, const float* R, int64_t ldr, int N, int F, int P, float* G, int64_t ldg,
+                float* gb, float* ws, int64_t ws_bytes, fer_stream_t stream);
+
 /* Column sums: out[n] (+)= scale * sum_m x[m][n]  (bias gradients). ws >= fer_colsum_ws(M,N). */
 int64_t fer_colsum_ws(int M, int N);
 int fer_colsum(int dtype, const void* x, int64_t ldx, int M, int N, float* out, int accumulate,
