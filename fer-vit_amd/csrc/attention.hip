@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "fervit_internal.h"
+#include "step_seed.h"
 
 namespace fer {
 
@@ -1927,8 +1928,6 @@ __global__ void attn_f32_grads(const float* P, const float* G, const float* qkv,
 }  // namespace fer
 
 using namespace fer;
-
-int fer::set_step_ptr_attention(const uint64_t* p) { return set_step_ptr_here(p) == hipSuccess ? 0 : -1; }
 
 #ifdef FER_ATTN_STAMPS
 extern "C" int fer_debug_attn_stamps(unsigned long long* host) {

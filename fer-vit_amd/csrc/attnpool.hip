@@ -13,6 +13,7 @@
 // are bit-identical. L is limited by the LDS arrays (FER_ATTNPOOL_MAX_L).
 #include "common.h"
 #include "fervit_internal.h"
+#include "step_seed.h"
 
 namespace fer {
 
@@ -191,8 +192,6 @@ __global__ __launch_bounds__(256) void relu_dropout_kernel(const T* __restrict__
 }  // namespace fer
 
 using namespace fer;
-
-int fer::set_step_ptr_attnpool(const uint64_t* p) { return set_step_ptr_here(p) == hipSuccess ? 0 : -1; }
 
 extern "C" int fer_attnpool_fwd(int dtype, const void* x, int64_t ldx, const float* w, const float* bias, void* y,
                                 int64_t ldy, float* probs, int B, int L, int C, fer_stream_t stream) {

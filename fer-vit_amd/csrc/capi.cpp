@@ -42,6 +42,24 @@ int num_cus() {
   return n;
 }
 
+// Step-counter setters, one per code object that includes step_seed.h, registered by static
+// constructors at load: a function-local, constant-initialised array (no heap, valid whichever
+// translation unit's constructors run first). n counts every registration, kept or not.
+constexpr int kStepSetters = 32;
+struct StepSetters {
+  hipError_t (*set[kStepSetters])(const uint64_t*);
+  int n;
+};
+static StepSetters& step_setters() {
+  static StepSetters s = {};
+  return s;
+}
+void register_step_ptr_setter(hipError_t (*set)(const uint64_t*)) {
+  StepSetters& s = step_setters();
+  if (s.n < kStepSetters) s.set[s.n] = set;
+  ++s.n;
+}
+
 }  // namespace fer
 
 extern "C" int fer_set_persistent_mode(int mode) {
@@ -148,12 +166,11 @@ extern "C" int fer_svm_xtr(const float* X, int64_t ldx, const float* R, int64_t 
 }
 
 extern "C" int fer_set_step_counter(const uint64_t* counter) {
-  // every code object that has dropout kernels keeps its own copy of the pointer
-  if (fer::set_step_ptr_gemm(counter) || fer::set_step_ptr_attention(counter) ||
-      fer::set_step_ptr_layernorm(counter) || fer::set_step_ptr_misc(counter) ||
-      fer::set_step_ptr_convbn(counter) || fer::set_step_ptr_attnpool(counter) ||
-      fer::set_step_ptr_conv2d(counter))
-    return fer::set_error("set_step_counter: hipMemcpyToSymbol failed");
+  // every code object that has dropout kernels keeps its own copy of the pointer (step_seed.h)
+  const fer::StepSetters& s = fer::step_setters();
+  if (s.n > fer::kStepSetters) return fer::set_error("set_step_counter: more code objects than the registry holds");
+  for (int i = 0; i < s.n; ++i)
+    if (s.set[i](counter) != hipSuccess) return fer::set_error("set_step_counter: hipMemcpyToSymbol failed");
   return 0;
 }
 

@@ -244,24 +244,8 @@ FER_DEV uint32_t fer_mix_pre(uint32_t x, uint32_t& lo) {
 FER_DEV uint32_t fer_hash(uint64_t seed, uint32_t pair) {
   return fer_mix((pair ^ (uint32_t)seed) + (uint32_t)(seed >> 32));
 }
-// Device-side step counter for graph-replayed training steps (fer_set_step_counter): a
-// captured launch keeps its host seed, so every dropout kernel mixes the current step into it.
-// One pointer per code object (each .hip file is its own code object); null = no counter.
-static __device__ const uint64_t* fer_step_ptr = nullptr;
-FER_DEV uint64_t step_seed(uint64_t seed) {
-  const uint64_t* p = fer_step_ptr;
-  if (!p) return seed;
-  // global-typed load (a generic pointer compiles to a flat load: vmcnt AND lgkmcnt waits)
-  const uint64_t c = *(const __attribute__((address_space(1))) uint64_t*)(const void*)p;
-  uint64_t z = seed ^ (c * 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// host side, per code object
-static inline hipError_t set_step_ptr_here(const uint64_t* p) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(fer_step_ptr), &p, sizeof(p));
-}
+// (A kernel whose launches are captured into a replayed graph first mixes the device step counter
+// into its seed: step_seed.h.)
 FER_DEV bool drop_keep(uint64_t seed, uint32_t idx, uint32_t thresh) {
   if (thresh == 0u) return true;
   const uint32_t h = fer_hash(seed, idx >> 1);

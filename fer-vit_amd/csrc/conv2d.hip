@@ -15,6 +15,7 @@
 // fixed-order loop, so repeat calls are bit-identical.
 #include "common.h"
 #include "fervit_internal.h"
+#include "step_seed.h"
 
 namespace fer {
 
@@ -329,8 +330,6 @@ __global__ __launch_bounds__(256) void pool2_chdrop_bwd_kernel(const T* __restri
 }  // namespace fer
 
 using namespace fer;
-
-int fer::set_step_ptr_conv2d(const uint64_t* p) { return set_step_ptr_here(p) == hipSuccess ? 0 : -1; }
 
 // B*H*W as a long, or -1 when a factor is < 1 or the product leaves 2^40 (far beyond any operand)
 static long pixels(int B, int H, int W) {

@@ -16,6 +16,7 @@
 // them. Repeat calls are bit-identical. C = 512 gives 64 (bf16) or 128 (fp32) workgroups.
 #include "common.h"
 #include "fervit_internal.h"
+#include "step_seed.h"
 
 namespace fer {
 
@@ -347,8 +348,6 @@ __global__ __launch_bounds__(256) void logits_bwd_kernel(const T* __restrict__ x
 }  // namespace fer
 
 using namespace fer;
-
-int fer::set_step_ptr_convbn(const uint64_t* p) { return set_step_ptr_here(p) == hipSuccess ? 0 : -1; }
 
 extern "C" int fer_conv1d_cols(int dtype, const void* x, int64_t ldx, void* cols, int64_t ldc, int B, int L, int C,
                                fer_stream_t stream) {

@@ -25,14 +25,9 @@ struct GemmArgs {
 };
 
 int set_error(const char* msg);
-// per-code-object setters of the device step-counter pointer (common.h step_seed)
-int set_step_ptr_gemm(const uint64_t* p);
-int set_step_ptr_attention(const uint64_t* p);
-int set_step_ptr_layernorm(const uint64_t* p);
-int set_step_ptr_misc(const uint64_t* p);
-int set_step_ptr_convbn(const uint64_t* p);
-int set_step_ptr_attnpool(const uint64_t* p);
-int set_step_ptr_conv2d(const uint64_t* p);
+// step_seed.h hands each including code object's setter of its device step-counter pointer to the
+// registry that fer_set_step_counter walks (capi.cpp); called from static constructors, no HIP call
+void register_step_ptr_setter(hipError_t (*set)(const uint64_t*));
 int hip_check(const char* what);
 // persistent GEMM / attention kernels: walk a fixed blockIdx stride instead of the work queue
 // (fer_set_persistent_mode(1))
@@ -55,11 +50,11 @@ void svm_forward_launch(const float* X, long ldx, const float* W, long ldw, cons
 void svm_xtr_launch(const float* X, long ldx, const float* R, long ldr, int N, int F, int P, float* G, long ldg,
                     float* gb, float* ws, hipStream_t st);
 inline int ceil_div(long a, long b);
-// out_k[c % seg] (+)= scale * sum_b part[b*ld + c]  (deterministic, misc.hip)
+// out_k[c % seg] (+)= scale * sum_b part[b*ld + c]  (deterministic, reduce.hip)
 void part_reduce(const float* part, int nb, long ld, int ncols, int seg, float* o0, float* o1, float* o2,
                  int accumulate, const float* scale, hipStream_t st);
 // Workspace for column partials that part_reduce will sum: inside fer_reduce_defer's window (same
-// stream, a shape the batched reduction takes) a slice of the deferral arena, else ws itself (misc.hip)
+// stream, a shape the batched reduction takes) a slice of the deferral arena, else ws itself (reduce.hip)
 float* reduction_ws(float* ws, size_t bytes, int ncols, hipStream_t st);
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
@@ -75,6 +70,8 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // a [rows][C] operand read or written in 16-byte pieces
 inline bool piece_ok(const void* p, int64_t ld, int C, int V) { return p && al16(p) && ld >= C && ld % V == 0; }
 inline int blocks_for(long n) { return (int)((n + 255) / 256); }
+// blocks of 256 threads for a grid-stride loop over n items (vit_edge.hip, wplus.hip, optim.hip)
+inline int grid_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 8192)); }
 // one thread per work item, 256 per block: the block count must fit the grid's 31 bits
 inline bool too_many(long n) { return n > 0x7FFFFFFFL * 256; }
 // elements of a 16-byte piece

@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "fervit_internal.h"
+#include "step_seed.h"
 
 namespace fer {
 
@@ -2173,8 +2174,6 @@ extern "C" int fer_wgrad_group(const fer_wgrad_item* items, int n, int splits, f
   hipLaunchKernelGGL((gemm_wgrad_group_kernel<2, 2>), dim3(tile0, S), dim3(256), 0, st, g);
   return hip_check("wgrad_group");
 }
-
-int fer::set_step_ptr_gemm(const uint64_t* p) { return set_step_ptr_here(p) == hipSuccess ? 0 : -1; }
 
 extern "C" int64_t fer_gemm_colsum_ws(int M, int N) {
   // tile partials (128-row tiles at most) or the stand-alone colsum pass's partials

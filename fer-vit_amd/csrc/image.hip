@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256) void image_augment_kernel(const uint8_t* __res
 // per-image random parameters (torchvision's get_params ranges), counter-hash draws
 FER_DEV float hu(uint64_t seed, uint32_t k) { return ((float)(fer_hash(seed, k) >> 8) + 0.5f) * (1.f / 16777216.f); }
 __global__ void image_aug_draw_kernel(float* __restrict__ prm, int B, int S, fer_image_aug a, uint64_t seed) {
-  seed = step_seed(seed);
+  // (draws take a fresh host seed per call and are not part of a captured step: no step_seed)
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   float* P = prm + (long)b * IMG_NP;

@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "fervit_internal.h"
+#include "step_seed.h"
 
 namespace fer {
 
@@ -389,8 +390,6 @@ static int ln_bwd_blocks(int M) {
 }  // namespace fer
 
 using namespace fer;
-
-int fer::set_step_ptr_layernorm(const uint64_t* p) { return set_step_ptr_here(p) == hipSuccess ? 0 : -1; }
 
 extern "C" int fer_layernorm_fwd(int dtype, const void* x, int64_t ldx, const float* gamma, const float* beta,
                                  int gamma_rows, int row_div, void* y, int64_t ldy, float* mean, float* rstd, int M,

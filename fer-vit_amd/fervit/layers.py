@@ -102,7 +102,7 @@ def _targets(flat: FlatParams, params: Sequence[torch.nn.Parameter], needs: Sequ
 
 
 class _ReduceDefer:
-    """Deferred bias / LayerNorm gradient reductions over one backward pass (csrc/misc.hip
+    """Deferred bias / LayerNorm gradient reductions over one backward pass (csrc/reduce.hip
     fer_reduce_defer). Inside a layer's backward the LayerNorm / attention / fused-GEMM column
     partials go to a persistent arena and their fixed-order sums (`part_reduce`, ~4-5 per layer,
     each a short dependent launch on the compute stream) are queued; the end of the backward (an

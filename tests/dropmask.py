@@ -59,7 +59,7 @@ def keep_mask_torch(seed: int, shape, p: float, device="cuda") -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------- latent augmentation draws
-# csrc/misc.hip latent_augment_kernel: three streams keyed by sub-seeds of the call's seed (step counter
+# csrc/wplus.hip latent_augment_kernel: three streams keyed by sub-seeds of the call's seed (step counter
 # unset), each a fer_hash of a 32-bit counter mapped to (0, 1] by u01.
 SCALE_XOR = 0x5851F42D4C957F2D
 MASK_XOR = 0x14057B7EF767814F
@@ -71,7 +71,7 @@ def sub_seeds(seed: int):
 
 
 def u01(h: np.ndarray) -> np.ndarray:
-    """csrc/misc.hip u01 in the kernel's own float32 arithmetic: ((float)(h >> 8) + 0.5f) * 2^-24. The sum
+    """csrc/wplus.hip u01 in the kernel's own float32 arithmetic: ((float)(h >> 8) + 0.5f) * 2^-24. The sum
     is rounded to float32 (to even above 2^23), so the top value is 1.0 and the bottom one 2^-25."""
     k = (_u32(h) >> np.uint64(8)).astype(np.float32)
     return (k + np.float32(0.5)) * np.float32(1.0 / 16777216.0)

@@ -1,5 +1,5 @@
-"""Element-wise checks of the kernels at the two ends of every model (csrc/misc.hip): patch im2col, token
-assembly and its gradient, the classification head, the w+ prologue (SemanticPE, LayerWiseNorm, LEAM), the
+"""Element-wise checks of the kernels at the two ends of every model (csrc/vit_edge.hip, csrc/wplus.hip): patch
+im2col, token assembly and its gradient, the classification head, the w+ prologue (SemanticPE, LayerWiseNorm, LEAM), the
 LatentDecomposer projection and the latent augmentation, on every dispatch branch, through the raw C ABI.
 
 Conventions of tests/test_gpu_rowops.py (DESIGN.md sections 2.1 and 2.6):

@@ -579,7 +579,7 @@ def test_tokens_bwd_dropout(dtype, D, B):
     """Gradient of the token assembly (cat(cls, patches) + pos, dropout): d(patches), d(cls) and
     d(pos) against the host keep mask; bf16 with D % 8 == 0 takes the 8-column kernel (B = 41: 16 batch
     chunks of 3, the last ones short or empty), other D % 4 == 0 the 4-column one, D = 6 the per-element
-    one (csrc/misc.hip tokens_bwd8_kernel / tokens_bwd4_kernel / tokens_bwd_kernel)."""
+    one (csrc/vit_edge.hip tokens_bwd8_kernel / tokens_bwd4_kernel / tokens_bwd_kernel)."""
     o = ops()
     n, p, seed = 9, 0.1, 777
     N = n + 1
@@ -760,7 +760,7 @@ def test_gemm_work_queue_every_tile_written():
 @pytest.mark.parametrize("D", [768, 388])
 def test_tokens_fwd_bf16_dropout(D):
     """Token assembly t = dropout(cat(cls, patches) + pos) on the bf16 path: D % 8 == 0 takes the 8-column
-    kernel (csrc/misc.hip tokens_fwd8_kernel), D = 388 the 4-column one; values and keep bits against the
+    kernel (csrc/vit_edge.hip tokens_fwd8_kernel), D = 388 the 4-column one; values and keep bits against the
     host keep mask (the same element index row * D + d in both kernels)."""
     o = ops()
     B, n, p, seed = 6, 13, 0.1, 4242

@@ -1,4 +1,4 @@
-"""Element-wise checks of the fused AdamW (fer_adamw, csrc/misc.hip adamw_kernel) and of the transposed bf16
+"""Element-wise checks of the fused AdamW (fer_adamw, csrc/optim.hip adamw_kernel) and of the transposed bf16
 weight shadow (fer_transpose_bf16_segments, transpose_segs_kernel) through the raw C ABI, with hand-built
 segment tables over one flat buffer.
 

@@ -1,4 +1,4 @@
-"""Deferred gradient reductions (fervit.layers._ReduceDefer, csrc/misc.hip fer_reduce_defer): the
+"""Deferred gradient reductions (fervit.layers._ReduceDefer, csrc/reduce.hip fer_reduce_defer): the
 bias / LayerNorm / attention-bias gradients of a backward with the queued, batched fixed-order sums
 are bit-identical to the immediate per-kernel reductions (same per-column arithmetic), for every
 model family, both precisions, with dropout on (train mode) where the family has it."""

@@ -1,5 +1,5 @@
 """Element-wise checks of the row kernels (csrc/layernorm.hip) and the small element / reduction
-kernels (csrc/misc.hip) against plain float64 formulas on the CPU, on every dispatch branch.
+kernels (csrc/optim.hip, csrc/reduce.hip, csrc/vit_edge.hip) against plain float64 formulas on the CPU, on every dispatch branch.
 
 Every comparison is per element: |got - ref| <= out_round * |ref| + c * 2^-23 * scale_i.
   * ref is float64 torch on the CPU, computed from the exact values the kernel was handed (bf16
