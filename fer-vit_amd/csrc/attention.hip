@@ -1946,34 +1946,106 @@ extern "C" int64_t fer_attention_ws(int dtype, int B, int N, int H) {
   return (dtype == FER_F32 ? (int64_t)2 * B * H * N * N * 4 : 0) + cs;
 }
 
-static bool pers_path(int dtype, int N, int dh) { return dtype == FER_BF16 && N <= 224 && dh <= 64; }
-// forward kernel for N <= 224, dh <= 64 (fer_attention_set_fwd_kernel): 0 automatic (the occupancy form
+// forward kernel of the PERS family (fer_attention_set_fwd_kernel): 0 automatic (the occupancy form
 // from 4 query blocks up with dropout on -- ViT-B/16's N = 197: 36.57 vs 36.87 ms per step on one box,
 // profiles/r05d_*; alone 116 vs 125-139 us at p = 0.1 -- the persistent kernel without dropout (82 vs
 // 90 us at p = 0, profiles/r06e_attn_fwd_spill_ab.txt: its producer wave hides the K / V loads and no
 // hashing VALU is left for the occupancy form's extra waves to hide) and below 4 query blocks, where
 // its occupancy-sized grids were tuned for the w+ / 48 px token counts), 1 persistent, 2 occupancy form
 static int g_fwd_kernel = 0;
+
+// Which kernels a call runs and what it keeps for the backward: the one statement of the rule.
+// fer_attention_saved_floats, the forward (which writes the keep bits) and the backward (which reads
+// them) take every such decision from attn_plan().
+enum AttnFamily {
+  ATTN_F32,     // the fp32 parity kernels
+  ATTN_PERS,    // up to 7 blocks of 32 tokens: attn_fwd_pers / attn_fwd_occ and attn_bwd_pers<NB>
+  ATTN_FUSED8,  // eight blocks: attn_fwd_bf16 / attn_bwd_fused_bf16 (a 9th wave would not fit 2/SIMD)
+  ATTN_GEN,     // any N, dh <= 128: attn_fwd_gen / attn_dq_gen / attn_dkv_gen<DH2>
+};
+struct AttnPlan {
+  AttnFamily family;
+  int nb;          // 32-token blocks of N (PERS: the NB instantiation)
+  int dh2;         // GEN: the dh variant, 1 up to dh = 64, else 2
+  bool fwd_occ;    // PERS: the forward runs the occupancy form
+  bool keep_bits;  // the forward stores the dropout keep bits behind lse, the backward reads them
+};
+static AttnPlan attn_plan(int dtype, int N, int dh, uint32_t drop_thresh, int fwd_kernel) {
+  AttnPlan p{ATTN_F32, (N + 31) / 32, dh <= 64 ? 1 : 2, false, false};
+  if (dtype == FER_F32) return p;
+  p.family = (p.dh2 == 2 || N > 256) ? ATTN_GEN : (N > 224 ? ATTN_FUSED8 : ATTN_PERS);
+  if (p.family != ATTN_PERS) return p;
+  p.fwd_occ = fwd_kernel == 2 || (fwd_kernel == 0 && drop_thresh && p.nb >= 4);
+  p.keep_bits = drop_thresh != 0;
+  return p;
+}
+// the NB instantiations of the PERS kernels
+template <typename F>
+static bool with_nb(int nb, F&& f) { return dispatch_int<1, 2, 3, 4, 5, 6, 7>(nb, f); }
+
+// saved state: lse [B*H*N, padded to 64 floats], then the keep bits [B*H][nb][nb][32] words
 static int64_t lse_floats(int B, int N, int H) { return ((int64_t)B * H * N + 63) / 64 * 64; }
-// persistent kernels walk a fixed blockIdx stride instead of the work queue (fer_set_persistent_mode)
-static bool fixed_stride() { return fixed_stride_mode(); }
+static int64_t saved_floats_of(const AttnPlan& p, int B, int N, int H) {
+  return lse_floats(B, N, H) + (p.keep_bits ? (int64_t)B * H * p.nb * p.nb * 32 : 0);
+}
+static uint32_t* keep_mask(const AttnPlan& p, const float* lse, int B, int N, int H) {
+  return p.keep_bits ? (uint32_t*)(lse + lse_floats(B, N, H)) : nullptr;
+}
 
 // Workgroups per CU a persistent attention kernel can hold (registers / LDS; the occupancy API,
-// queried once per instantiation): the small-N instantiations (w+ latents: N = 19, one key block)
-// are one or two waves and fit several to a CU, so their persistent grid is CUs x this, not CUs --
-// one wave per CU left the latent-ViT attention latency-bound.
+// queried once per instantiation, from a function-local static at the launch): the small-N
+// instantiations (w+ latents: N = 19, one key block) are one or two waves and fit several to a CU, so
+// their persistent grid is CUs x this, not CUs -- one wave per CU left the latent-ViT attention
+// latency-bound.
 template <typename Kern>
 static int pers_occ(Kern k, int threads) {
   int n = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, threads, 0) != hipSuccess || n < 1) n = 1;
   return std::min(n, 8);
 }
+// grid of a persistent launch over B * H heads, and its work queue (none: a fixed blockIdx stride,
+// fer_set_persistent_mode)
+static WqArgs pers_grid(int heads, int occ, hipStream_t st, int* grid) {
+  *grid = std::min(heads, num_cus() * occ);
+  return fixed_stride_mode() ? WqArgs{} : wq_prepare_here(st, *grid, heads);
+}
+
+// What the bf16 forward and backward ask of their arguments; `what` is the entry's name. lds: each
+// leading dimension with the element multiple it needs; the two entries word the ld and the 2 GiB
+// error differently (ld_msg, span_msg).
+struct LdArg {
+  int64_t ld;
+  int mult;
+};
+static int check_bf16_args(const char* what, int B, int N, int H, int dh, uint32_t drop_thresh,
+                           std::initializer_list<LdArg> lds, const char* ld_msg, const char* span_msg) {
+  auto fail = [&](const char* tag, const char* text) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s%s: %s", what, tag, text);
+    return set_error(msg);
+  };
+  if (dh > 128 || dh % 8) return fail("(bf16)", "needs dh <= 128, dh % 8 == 0");
+  if (check_drop_range(drop_thresh, (long)B * H * N * (N + (N & 1)), what))
+    return fail("", "dropout over >= 2^32 probabilities");
+  for (const LdArg& a : lds)
+    if (a.ld % a.mult) return fail("(bf16)", ld_msg);
+  // (the kernels address their operands through 32-bit buffer offsets, bit 31 = out of range)
+  for (const LdArg& a : lds)
+    if ((long)B * N * a.ld * 2 >= 0x7FFFFFF0L) return fail("(bf16)", span_msg);
+  return 0;
+}
+
+// fp32: P = softmax(scale q k^T) [B*H*N][N]; lse (or null) gets the rows' log-sum-exp
+static void f32_probs(const float* qkv, long ld_qkv, float* P, float* lse, int B, int N, int H, int dh, float scale,
+                      hipStream_t st) {
+  const long pe = (long)B * H * N * N, rows = (long)B * H * N;
+  hipLaunchKernelGGL(attn_f32_scores, dim3(ceil_div(pe, 256)), dim3(256), 0, st, qkv, ld_qkv, P, B, N, H, dh, scale);
+  hipLaunchKernelGGL(attn_f32_softmax, dim3(ceil_div(rows, 256)), dim3(256), 0, st, P, lse, rows, N);
+}
 
 extern "C" int64_t fer_attention_saved_floats(int dtype, int B, int N, int H, int dh, uint32_t drop_thresh) {
   if (check_dtype(dtype, "attention_saved_floats: unknown dtype")) return -1;
-  const int64_t nb = (N + 31) / 32;
-  const int64_t mask_words = (drop_thresh && pers_path(dtype, N, dh)) ? (int64_t)B * H * nb * nb * 32 : 0;
-  return lse_floats(B, N, H) + mask_words;
+  return saved_floats_of(attn_plan(dtype, N, dh, drop_thresh, g_fwd_kernel), B, N, H);
 }
 
 extern "C" int fer_attention_fwd(int dtype, const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, float* lse,
@@ -1982,74 +2054,50 @@ extern "C" int fer_attention_fwd(int dtype, const void* qkv, int64_t ld_qkv, voi
   if (check_dtype(dtype, "attention_fwd: unknown dtype")) return -1;
   if (B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (saved_floats < fer_attention_saved_floats(dtype, B, N, H, dh, drop_thresh))
+  const AttnPlan p = attn_plan(dtype, N, dh, drop_thresh, g_fwd_kernel);
+  if (saved_floats < saved_floats_of(p, B, N, H))
     return set_error("attention_fwd: saved-state buffer smaller than fer_attention_saved_floats()");
-  if (dtype == FER_F32) {
+  if (p.family == ATTN_F32) {
     if (!ws || ws_bytes < fer_attention_ws(dtype, B, N, H)) return set_error("attention_fwd: fp32 workspace too small");
-    const long pe = (long)B * H * N * N, rows = (long)B * H * N, oe = rows * dh;
-    hipLaunchKernelGGL(attn_f32_scores, dim3(ceil_div(pe, 256)), dim3(256), 0, st, (const float*)qkv, (long)ld_qkv, ws,
-                       B, N, H, dh, scale);
-    hipLaunchKernelGGL(attn_f32_softmax, dim3(ceil_div(rows, 256)), dim3(256), 0, st, ws, lse, rows, N);
-    hipLaunchKernelGGL(attn_f32_pv, dim3(ceil_div(oe, 256)), dim3(256), 0, st, (const float*)ws, (const float*)qkv,
-                       (long)ld_qkv, (float*)out, (long)ld_out, B, N, H, dh, drop_thresh, drop_scale, seed);
+    f32_probs((const float*)qkv, ld_qkv, ws, lse, B, N, H, dh, scale, st);
+    hipLaunchKernelGGL(attn_f32_pv, dim3(ceil_div((long)B * H * N * dh, 256)), dim3(256), 0, st, (const float*)ws,
+                       (const float*)qkv, (long)ld_qkv, (float*)out, (long)ld_out, B, N, H, dh, drop_thresh, drop_scale,
+                       seed);
     return hip_check("attention_fwd_f32");
   }
-  if (dh > 128 || dh % 8) return set_error("attention_fwd(bf16): needs dh <= 128, dh % 8 == 0");
-  if (check_drop_range(drop_thresh, (long)B * H * N * (N + (N & 1)), "attention_fwd: dropout over >= 2^32 probabilities"))
+  if (check_bf16_args("attention_fwd", B, N, H, dh, drop_thresh, {{ld_qkv, 8}, {ld_out, 4}},
+                      "misaligned leading dimension", "qkv or out exceeds 2 GiB"))
     return -1;
-  if (ld_qkv % 8 || ld_out % 4) return set_error("attention_fwd(bf16): misaligned leading dimension");
-  // (the persistent kernel addresses qkv and out through 32-bit buffer offsets, bit 31 = out of range)
-  if ((long)B * N * ld_qkv * 2 >= 0x7FFFFFF0L || (long)B * N * ld_out * 2 >= 0x7FFFFFF0L)
-    return set_error("attention_fwd(bf16): qkv or out exceeds 2 GiB");
+  const bf16* q = (const bf16*)qkv;
+  bf16* o = (bf16*)out;
+  const long ldq = ld_qkv, ldo = ld_out;
   const float sl2 = scale * LOG2E;
-  if (N <= 256 && dh <= 64 && N > 224) {  // NB = 8: 9 waves would not fit 2/SIMD
-    hipLaunchKernelGGL(attn_fwd_bf16, dim3(B * H), dim3(512), 0, st, (const bf16*)qkv, (long)ld_qkv, (bf16*)out,
-                       (long)ld_out, lse, N, H, dh, sl2, drop_thresh, drop_scale, seed);
-  } else if (N <= 224 && dh <= 64 && (g_fwd_kernel == 2 || (g_fwd_kernel == 0 && drop_thresh && (N + 31) / 32 >= 4))) {
-    const int nb = (N + 31) / 32;
-    uint32_t* mask = (drop_thresh && pers_path(dtype, N, dh)) ? (uint32_t*)(lse + lse_floats(B, N, H)) : nullptr;
-#define FER_FOCC2(NBV)                                                                                     \
-  case NBV:                                                                                                \
-    hipLaunchKernelGGL((attn_fwd_occ<NBV>), dim3(B * H), dim3(64 * NBV), 0, st, (const bf16*)qkv,          \
-                       (long)ld_qkv, (bf16*)out, (long)ld_out, lse, mask, N, H, dh, sl2, drop_thresh,       \
-                       drop_scale, seed);                                                                  \
-    break;
-    switch (nb) {
-      FER_FOCC2(1) FER_FOCC2(2) FER_FOCC2(3) FER_FOCC2(4) FER_FOCC2(5) FER_FOCC2(6) FER_FOCC2(7)
-    }
-#undef FER_FOCC2
-  } else if (N <= 224 && dh <= 64) {
-    const int nb = (N + 31) / 32;
-    uint32_t* mask = (drop_thresh && pers_path(dtype, N, dh)) ? (uint32_t*)(lse + lse_floats(B, N, H)) : nullptr;
-    int occ = 1;
-#define FER_FOCC(NBV)                                                               \
-  case NBV: {                                                                       \
-    static const int o = pers_occ(attn_fwd_pers<NBV>, 64 * (NBV + 1));             \
-    occ = o;                                                                        \
-  } break;
-    switch (nb) { FER_FOCC(1) FER_FOCC(2) FER_FOCC(3) FER_FOCC(4) FER_FOCC(5) FER_FOCC(6) FER_FOCC(7) }
-#undef FER_FOCC
-    const int grid = std::min(B * H, num_cus() * occ);
-    const WqArgs wq = fixed_stride() ? WqArgs{} : wq_prepare_here(st, grid, B * H);
-#define FER_FPERS(NBV)                                                                                     \
-  case NBV:                                                                                                \
-    hipLaunchKernelGGL((attn_fwd_pers<NBV>), dim3(grid), dim3(64 * (NBV + 1)), 0, st, (const bf16*)qkv,    \
-                       (long)ld_qkv, (bf16*)out, (long)ld_out, lse, mask, B * H, N, H, dh, sl2, drop_thresh, \
-                       drop_scale, seed, wq);                                                             \
-    break;
-    switch (nb) {
-      FER_FPERS(1) FER_FPERS(2) FER_FPERS(3) FER_FPERS(4) FER_FPERS(5) FER_FPERS(6) FER_FPERS(7)
-    }
-#undef FER_FPERS
-    wq_check_launch(st, wq);
+  uint32_t* mask = keep_mask(p, lse, B, N, H);
+  if (p.family == ATTN_FUSED8) {
+    hipLaunchKernelGGL(attn_fwd_bf16, dim3(B * H), dim3(512), 0, st, q, ldq, o, ldo, lse, N, H, dh, sl2, drop_thresh,
+                       drop_scale, seed);
+  } else if (p.fwd_occ) {
+    with_nb(p.nb, [&](auto I) {
+      constexpr int NB = decltype(I)::value;
+      hipLaunchKernelGGL(attn_fwd_occ<NB>, dim3(B * H), dim3(64 * NB), 0, st, q, ldq, o, ldo, lse, mask, N, H, dh, sl2,
+                         drop_thresh, drop_scale, seed);
+    });
+  } else if (p.family == ATTN_PERS) {
+    with_nb(p.nb, [&](auto I) {
+      constexpr int NB = decltype(I)::value;
+      static const int occ = pers_occ(attn_fwd_pers<NB>, 64 * (NB + 1));
+      int grid;
+      const WqArgs wq = pers_grid(B * H, occ, st, &grid);
+      hipLaunchKernelGGL(attn_fwd_pers<NB>, dim3(grid), dim3(64 * (NB + 1)), 0, st, q, ldq, o, ldo, lse, mask, B * H, N,
+                         H, dh, sl2, drop_thresh, drop_scale, seed, wq);
+      wq_check_launch(st, wq);
+    });
   } else {
     const dim3 grid(B * H, (N + GEN_ROWS - 1) / GEN_ROWS);
-    if (dh <= 64)
-      hipLaunchKernelGGL(attn_fwd_gen<1>, grid, dim3(256), 0, st, (const bf16*)qkv, (long)ld_qkv, (bf16*)out,
-                         (long)ld_out, lse, N, H, dh, sl2, drop_thresh, drop_scale, seed);
-    else
-      hipLaunchKernelGGL(attn_fwd_gen<2>, grid, dim3(256), 0, st, (const bf16*)qkv, (long)ld_qkv, (bf16*)out,
-                         (long)ld_out, lse, N, H, dh, sl2, drop_thresh, drop_scale, seed);
+    dispatch_int<1, 2>(p.dh2, [&](auto I) {
+      hipLaunchKernelGGL(attn_fwd_gen<decltype(I)::value>, grid, dim3(256), 0, st, q, ldq, o, ldo, lse, N, H, dh, sl2,
+                         drop_thresh, drop_scale, seed);
+    });
   }
   return hip_check("attention_fwd_bf16");
 }
@@ -2062,7 +2110,8 @@ extern "C" int fer_attention_bwd(int dtype, const void* qkv, int64_t ld_qkv, con
   if (check_dtype(dtype, "attention_bwd: unknown dtype")) return -1;
   if (B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (saved_floats < fer_attention_saved_floats(dtype, B, N, H, dh, drop_thresh))
+  const AttnPlan p = attn_plan(dtype, N, dh, drop_thresh, g_fwd_kernel);
+  if (saved_floats < saved_floats_of(p, B, N, H))
     return set_error("attention_bwd: saved-state buffer smaller than fer_attention_saved_floats()");
   const int D3 = 3 * H * dh;
   if (colsum && (!ws || ws_bytes < fer_attention_ws(dtype, B, N, H)))
@@ -2071,14 +2120,19 @@ extern "C" int fer_attention_bwd(int dtype, const void* qkv, int64_t ld_qkv, con
   auto colsum_pass = [&](float* cws, int64_t cbytes) -> int {
     return fer_colsum(dtype, dqkv, ld_dqkv, B * N, D3, colsum, colsum_accumulate, nullptr, cws, cbytes, stream);
   };
-  if (dtype == FER_F32) {
+  // ... summed from the kernel's partials [parts][D3] in ws (the fused and persistent kernels)
+  auto colsum_parts = [&](const char* what, int parts) -> int {
+    int rc = hip_check(what);
+    if (rc || !colsum) return rc;
+    part_reduce(ws, parts, D3, D3, D3, colsum, nullptr, nullptr, colsum_accumulate, nullptr, st);
+    return hip_check("attention_bwd_colsum");
+  };
+  if (p.family == ATTN_F32) {
     if (!ws || ws_bytes < fer_attention_ws(dtype, B, N, H)) return set_error("attention_bwd: fp32 workspace too small");
     const long pe = (long)B * H * N * N, rows = (long)B * H * N, oe = rows * dh;
     float* P = ws;
     float* G = ws + pe;
-    hipLaunchKernelGGL(attn_f32_scores, dim3(ceil_div(pe, 256)), dim3(256), 0, st, (const float*)qkv, (long)ld_qkv, P,
-                       B, N, H, dh, scale);
-    hipLaunchKernelGGL(attn_f32_softmax, dim3(ceil_div(rows, 256)), dim3(256), 0, st, P, (float*)nullptr, rows, N);
+    f32_probs((const float*)qkv, ld_qkv, P, nullptr, B, N, H, dh, scale, st);
     hipLaunchKernelGGL(attn_f32_ds, dim3(ceil_div(rows, 256)), dim3(256), 0, st, (const float*)P, G,
                        (const float*)qkv, (long)ld_qkv, (const float*)out, (long)ld_out, (const float*)dout,
                        (long)ld_dout, B, N, H, dh, drop_thresh, drop_scale, seed);
@@ -2089,70 +2143,41 @@ extern "C" int fer_attention_bwd(int dtype, const void* qkv, int64_t ld_qkv, con
     if (rc || !colsum) return rc;
     return colsum_pass(ws + 2 * pe, ws_bytes - 2 * pe * 4);
   }
-  if (dh > 128 || dh % 8) return set_error("attention_bwd(bf16): needs dh <= 128, dh % 8 == 0");
-  if (check_drop_range(drop_thresh, (long)B * H * N * (N + (N & 1)), "attention_bwd: dropout over >= 2^32 probabilities"))
+  if (check_bf16_args("attention_bwd", B, N, H, dh, drop_thresh, {{ld_qkv, 8}, {ld_out, 8}, {ld_dout, 8}, {ld_dqkv, 8}},
+                      "misaligned ld", "operand exceeds 2 GiB (buffer-resource range)"))
     return -1;
-  if (ld_qkv % 8 || ld_out % 8 || ld_dout % 8 || ld_dqkv % 8) return set_error("attention_bwd(bf16): misaligned ld");
-  if ((long)B * N * ld_qkv * 2 >= 0x7FFFFFF0L || (long)B * N * ld_dout * 2 >= 0x7FFFFFF0L ||
-      (long)B * N * ld_dqkv * 2 >= 0x7FFFFFF0L || (long)B * N * ld_out * 2 >= 0x7FFFFFF0L)
-    return set_error("attention_bwd(bf16): operand exceeds 2 GiB (buffer-resource range)");
-  const int nb = (N + 31) / 32;
+  const bf16 *q = (const bf16*)qkv, *o = (const bf16*)out, *g = (const bf16*)dout;
+  bf16* dq = (bf16*)dqkv;
+  const long ldq = ld_qkv, ldo = ld_out, ldg = ld_dout, lddq = ld_dqkv;
   const float sl2 = scale * LOG2E;
-  if (pers_path(dtype, N, dh)) {
-    const uint32_t* mask = drop_thresh ? (const uint32_t*)(lse + lse_floats(B, N, H)) : nullptr;
-    if (colsum) ws = reduction_ws(ws, (size_t)B * nb * D3 * 4, D3, st);
-    int occ = 1;
-#define FER_BOCC(NBV)                                                               \
-  case NBV: {                                                                       \
-    static const int o = pers_occ(attn_bwd_pers<NBV>, bwd_threads<NBV>());                   \
-    occ = o;                                                                        \
-  } break;
-    switch (nb) { FER_BOCC(1) FER_BOCC(2) FER_BOCC(3) FER_BOCC(4) FER_BOCC(5) FER_BOCC(6) FER_BOCC(7) }
-#undef FER_BOCC
-    const int grid = std::min(B * H, num_cus() * occ);
-    const WqArgs wq = fixed_stride() ? WqArgs{} : wq_prepare_here(st, grid, B * H);
-#define FER_PERS(NBV)                                                                                          \
-  case NBV:                                                                                                    \
-    hipLaunchKernelGGL(attn_bwd_pers<NBV>, dim3(grid), dim3(bwd_threads<NBV>()), 0, st, (const bf16*)qkv,                \
-                       (long)ld_qkv, (const bf16*)out, (long)ld_out, (const bf16*)dout, (long)ld_dout, lse, mask, \
-                       (bf16*)dqkv, (long)ld_dqkv, B * H, N, H, dh, scale, sl2, drop_scale, colsum ? ws : nullptr, \
-                       wq);                                                                                      \
-    break;
-    switch (nb) {
-      FER_PERS(1) FER_PERS(2) FER_PERS(3) FER_PERS(4) FER_PERS(5) FER_PERS(6) FER_PERS(7)
-    }
-#undef FER_PERS
-    wq_check_launch(st, wq);
-    int rc = hip_check("attention_bwd_bf16_pers");
-    if (rc || !colsum) return rc;
-    part_reduce(ws, B * nb, D3, D3, D3, colsum, nullptr, nullptr, colsum_accumulate, nullptr, st);
-    return hip_check("attention_bwd_colsum");
+  if (p.family == ATTN_PERS) {
+    const uint32_t* mask = keep_mask(p, lse, B, N, H);
+    if (colsum) ws = reduction_ws(ws, (size_t)B * p.nb * D3 * 4, D3, st);
+    with_nb(p.nb, [&](auto I) {
+      constexpr int NB = decltype(I)::value;
+      static const int occ = pers_occ(attn_bwd_pers<NB>, bwd_threads<NB>());
+      int grid;
+      const WqArgs wq = pers_grid(B * H, occ, st, &grid);
+      hipLaunchKernelGGL(attn_bwd_pers<NB>, dim3(grid), dim3(bwd_threads<NB>()), 0, st, q, ldq, o, ldo, g, ldg, lse, mask,
+                         dq, lddq, B * H, N, H, dh, scale, sl2, drop_scale, colsum ? ws : nullptr, wq);
+      wq_check_launch(st, wq);
+    });
+    return colsum_parts("attention_bwd_bf16_pers", B * p.nb);
   }
-  if (nb <= 8 && dh <= 64) {
+  if (p.family == ATTN_FUSED8) {
     if (colsum) ws = reduction_ws(ws, (size_t)B * D3 * 4, D3, st);
-    // 224 < N <= 256 (N <= 224 took the persistent path above): eight query blocks
-    hipLaunchKernelGGL(attn_bwd_fused_bf16, dim3(B * H), dim3(512), 0, st, (const bf16*)qkv, (long)ld_qkv,
-                       (const bf16*)out, (long)ld_out, (const bf16*)dout, (long)ld_dout, lse, (bf16*)dqkv,
-                       (long)ld_dqkv, N, H, dh, scale, sl2, drop_thresh, drop_scale, seed, colsum ? ws : nullptr);
-    int rc = hip_check("attention_bwd_bf16_fused");
-    if (rc || !colsum) return rc;
-    part_reduce(ws, B, D3, D3, D3, colsum, nullptr, nullptr, colsum_accumulate, nullptr, st);
-    return hip_check("attention_bwd_colsum");
+    hipLaunchKernelGGL(attn_bwd_fused_bf16, dim3(B * H), dim3(512), 0, st, q, ldq, o, ldo, g, ldg, lse, dq, lddq, N, H,
+                       dh, scale, sl2, drop_thresh, drop_scale, seed, colsum ? ws : nullptr);
+    return colsum_parts("attention_bwd_bf16_fused", B);
   }
   const dim3 grid(B * H, (N + GEN_ROWS - 1) / GEN_ROWS);
-#define FER_GEN(DH2)                                                                                           \
-  hipLaunchKernelGGL(attn_dq_gen<DH2>, grid, dim3(256), 0, st, (const bf16*)qkv, (long)ld_qkv, (const bf16*)out, \
-                     (long)ld_out, (const bf16*)dout, (long)ld_dout, lse, (bf16*)dqkv, (long)ld_dqkv, N, H, dh,    \
-                     scale, sl2, drop_thresh, drop_scale, seed);                                                \
-  hipLaunchKernelGGL(attn_dkv_gen<DH2>, grid, dim3(256), 0, st, (const bf16*)qkv, (long)ld_qkv, (const bf16*)out, \
-                     (long)ld_out, (const bf16*)dout, (long)ld_dout, lse, (bf16*)dqkv, (long)ld_dqkv, N, H, dh,     \
-                     scale, sl2, drop_thresh, drop_scale, seed);
-  if (dh <= 64) {
-    FER_GEN(1)
-  } else {
-    FER_GEN(2)
-  }
-#undef FER_GEN
+  dispatch_int<1, 2>(p.dh2, [&](auto I) {
+    constexpr int DH2 = decltype(I)::value;
+    hipLaunchKernelGGL(attn_dq_gen<DH2>, grid, dim3(256), 0, st, q, ldq, o, ldo, g, ldg, lse, dq, lddq, N, H, dh, scale,
+                       sl2, drop_thresh, drop_scale, seed);
+    hipLaunchKernelGGL(attn_dkv_gen<DH2>, grid, dim3(256), 0, st, q, ldq, o, ldo, g, ldg, lse, dq, lddq, N, H, dh, scale,
+                       sl2, drop_thresh, drop_scale, seed);
+  });
   int rc = hip_check("attention_bwd_bf16");
   if (rc || !colsum) return rc;
   return colsum_pass(ws, ws_bytes);

@@ -35,20 +35,6 @@ bool fixed_stride_mode();
 // compute units of the current device (256 when the query fails), asked once per process
 int num_cus();
 int gemm_launch(const GemmDesc& d, const EpiArgs& e, hipStream_t st);
-// evaluation metrics (metrics.hip): launches only, the entry points in capi.cpp check the arguments
-void cls_stats_launch(const float* logits, long ld, const int64_t* labels, int B, int C, int64_t* preds, float* conf,
-                      float* probs, long ld_probs, int64_t* confusion, int64_t* counters, hipStream_t st);
-void cls_report_launch(const int64_t* confusion, int C, double* out, hipStream_t st);
-void token_cosine_launch(int dtype, const void* tokens, long ld, int B, int N, int D, float eps, float* cls_sim,
-                         long ld_cls, float* tok_sim, long ld_tok, hipStream_t st);
-// linear-SVM passes (svm.hip): launches only, the entry points in capi.cpp check the arguments
-long svm_ws_bytes(int N, int F);
-void svm_forward_launch(const float* X, long ldx, const float* W, long ldw, const float* bias, int N, int F, int P,
-                        int hinge, const int64_t* labels, const int64_t* classes, const float* Cp, const float* Cn,
-                        float* Z, long ldz, float* R, long ldr, float* Dw, long ldd, float* loss, float* ws,
-                        hipStream_t st);
-void svm_xtr_launch(const float* X, long ldx, const float* R, long ldr, int N, int F, int P, float* G, long ldg,
-                    float* gb, float* ws, hipStream_t st);
 inline int ceil_div(long a, long b);
 // out_k[c % seg] (+)= scale * sum_b part[b*ld + c]  (deterministic, reduce.hip)
 void part_reduce(const float* part, int nb, long ld, int ncols, int seg, float* o0, float* o1, float* o2,
@@ -91,6 +77,19 @@ template <typename F>
 inline void with_dtype(int dtype, F&& f) {  // dtype has passed check_dtype
   if (dtype == FER_BF16) f(DtypeTag<__bf16>{});
   else f(DtypeTag<float>{});
+}
+
+// A run-time integer that selects a template instantiation (attention's NB and dh variants, the
+// GEMM epilogue kinds):
+//   dispatch_int<1, 2, 3>(v, [&](auto I) { constexpr int NB = decltype(I)::value; ... k<NB> ... });
+// calls f with the listed value equal to v; false when none is (f did not run). A left fold, so that f's
+// instantiations, and with them the kernels of the code object, come out in list order (a right fold
+// emits them reversed; the ViT-B step measured 0.09 ms slower with the attention and GEMM kernels laid
+// out in that order, DESIGN.md section 4 "Host dispatch").
+template <int V> struct IntTag { static constexpr int value = V; };
+template <int... Vs, typename F>
+inline bool dispatch_int(int v, F&& f) {
+  return (... || (v == Vs && (f(IntTag<Vs>{}), true)));
 }
 
 }  // namespace fer

@@ -1870,25 +1870,16 @@ static int launch_bf16(GemmArgs g, const EpiArgs& e, hipStream_t st) {
   g.tiles_m = (g.M + 127) / 128;
   g.tiles_n = (g.N + BN - 1) / BN;
   dim3 grid(g.tiles_m * g.tiles_n, g.splits);
-#define FER_BF16K(K) hipLaunchKernelGGL((gemm_bf16_kernel<128, BN, 2, 2, AKC, BKC, K>), grid, dim3(256), 0, st, g, e)
+  auto launch = [&](auto K) {
+    hipLaunchKernelGGL((gemm_bf16_kernel<128, BN, 2, 2, AKC, BKC, decltype(K)::value>), grid, dim3(256), 0, st, g, e);
+  };
   // the K-contiguous kernel (the small-grid configs: w+ latents, 48 px) also gets the
-  // fixed-flag epilogues (row operands through its LDS-DMA staging: the LDS-DMA kinds)
+  // fixed-flag epilogues (row operands through its LDS-DMA staging: RES2 / MUL2 run as RES / MUL)
   if constexpr (AKC && BKC) {
-    int ek = g.partial ? EPI_GEN : epi_kind(e, g.M, g.N);
-    if (ek == EPI_RES2) ek = EPI_RES;
-    if (ek == EPI_MUL2) ek = EPI_MUL;
-    switch (ek) {
-      case EPI_STORE: FER_BF16K(EPI_STORE); break;
-      case EPI_GATE: FER_BF16K(EPI_GATE); break;
-      case EPI_GATER: FER_BF16K(EPI_GATER); break;
-      case EPI_RES: FER_BF16K(EPI_RES); break;
-      case EPI_MUL: FER_BF16K(EPI_MUL); break;
-      default: FER_BF16K(EPI_GEN); break;
-    }
-  } else {
-    FER_BF16K(EPI_GEN);
+    const int ek = g.partial ? EPI_GEN : epi_base(epi_kind(e, g.M, g.N));
+    if (dispatch_int<EPI_STORE, EPI_GATE, EPI_GATER, EPI_RES, EPI_MUL>(ek, launch)) return 0;
   }
-#undef FER_BF16K
+  launch(IntTag<EPI_GEN>{});
   return 0;
 }
 
@@ -1904,8 +1895,6 @@ static int launch_ring(GemmArgs g, const EpiArgs& e, hipStream_t st) {
 
 template <bool AKC, bool BKC>
 static int launch_8ph(GemmArgs g, const EpiArgs& e, hipStream_t st) {
-  // fixed-flag epilogues for the K-contiguous kernel (the forward and transposed-shadow dgrad path)
-  const int ek = (AKC && BKC && !g.partial) ? epi_kind(e, g.M, g.N) : EPI_GEN;
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
   // persistent grid: one workgroup per CU (a multiple of 8: the XCD-aware tile order)
@@ -1919,27 +1908,20 @@ static int launch_8ph(GemmArgs g, const EpiArgs& e, hipStream_t st) {
     for (int c = 0; c < 8; ++c) g.tq_base[c] = w.base[c];
   }
   dim3 grid(gx, g.splits);
-#define FER_8PH(DY, K) hipLaunchKernelGGL((gemm_8ph_kernel<AKC, BKC, DY, K>), grid, dim3(512), 0, st, g, e)
-#define FER_8PH_K(DY)                                  \
-  if constexpr (AKC && BKC) {                          \
-    switch (ek) {                                      \
-      case EPI_STORE: FER_8PH(DY, EPI_STORE); break;   \
-      case EPI_GATE: FER_8PH(DY, EPI_GATE); break;     \
-      case EPI_GATER: FER_8PH(DY, EPI_GATER); break;   \
-      case EPI_RES2: FER_8PH(DY, EPI_RES2); break;     \
-      case EPI_MUL2: FER_8PH(DY, EPI_MUL2); break;     \
-      default: FER_8PH(DY, EPI_GEN); break;            \
-    }                                                  \
-  } else {                                             \
-    FER_8PH(DY, EPI_GEN);                              \
-  }
-  if (g.tq) {
-    FER_8PH_K(true)
-  } else {
-    FER_8PH_K(false)
-  }
-#undef FER_8PH_K
-#undef FER_8PH
+  // DY: the work-queue (1) or the fixed-stride (0) form of the kernel; K: its epilogue kind
+  auto launch = [&](auto DY, auto K) {
+    hipLaunchKernelGGL((gemm_8ph_kernel<AKC, BKC, decltype(DY)::value != 0, decltype(K)::value>), grid, dim3(512), 0,
+                       st, g, e);
+  };
+  dispatch_int<1, 0>(g.tq != nullptr, [&](auto DY) {
+    // fixed-flag epilogues for the K-contiguous kernel (the forward and transposed-shadow dgrad path; row
+    // operands straight into registers: RES2 / MUL2)
+    if constexpr (AKC && BKC) {
+      const int ek = g.partial ? EPI_GEN : epi_kind(e, g.M, g.N);
+      if (dispatch_int<EPI_STORE, EPI_GATE, EPI_GATER, EPI_RES2, EPI_MUL2>(ek, [&](auto K) { launch(DY, K); })) return;
+    }
+    launch(DY, IntTag<EPI_GEN>{});
+  });
   wq_check_launch(st, w);
   return 0;
 }
@@ -1976,8 +1958,6 @@ static bool use_128x64(long t128, long t64, int K) {
   X(11, false, (launch_bf16<(BKC ? 64 : 128), AKC, BKC>))
 
 static int g_forced_cfg = -1;  // fer_gemm_set_config; -1: automatic
-
-static int forced_cfg() { return g_forced_cfg; }
 
 static bool cfg_known(int c) {
 #define X(ID, IS256, LAUNCH) if (c == ID) return true;
@@ -2062,7 +2042,7 @@ int gemm_launch(const GemmDesc& d, const EpiArgs& e_in, hipStream_t st) {
   // (128^2, K-contiguous: split only below half a round; the ordered slab reduction costs more than the
   // idle CUs of an unsplit 152-228 tile grid -- latent fc2 fwd 50.7 -> 29.4 us, qkv dgrad 46.4 -> 22.9 us)
   const long tgt128k = (d.a_kc && d.b_kc) ? 256 : 512;
-  int cfg = forced_cfg();
+  int cfg = g_forced_cfg;
   if (cfg < 0) {
     if (d.K >= 8192 || t256 >= 256)  // big grids, and token-long weight gradients (split-K fills the GPU)
       // (MN x MN weight gradients split >= 16 ways -- out_proj / patch embed, 9 tiles x 28 splits --
@@ -2077,22 +2057,20 @@ int gemm_launch(const GemmDesc& d, const EpiArgs& e_in, hipStream_t st) {
     else  // fewer 256^2 tiles than CUs (latent / 48 px configs): 128^2 tiles, two workgroups per CU
       cfg = 3;
   }
-  int splits = cfg_is_256(cfg) ? splits_for(t256, (!d.a_kc && !d.b_kc) ? tgt256_mn : tgt256) : splits_for(t128, tgt128k);
+  const int bm = cfg_is_256(cfg) ? 256 : 128;  // tile height
+  int splits = bm == 256 ? splits_for(t256, (!d.a_kc && !d.b_kc) ? tgt256_mn : tgt256) : splits_for(t128, tgt128k);
   g.splits = splits;
   g.k_chunk = splits > 1 ? (((d.K + splits - 1) / splits + BK - 1) / BK) * BK : d.K;
   if (splits > 1) g.splits = (d.K + g.k_chunk - 1) / g.k_chunk;
   g.partial = g.splits > 1;
   g.ws = d.ws;
-  g.cs_part = e.colsum ? reduction_ws(d.ws, (size_t)((d.M + (cfg_is_256(cfg) ? 255 : 127)) / (cfg_is_256(cfg) ? 256 : 128)) * d.N * 4,
-                                      d.N, st)
-                       : nullptr;
+  g.cs_part = e.colsum ? reduction_ws(d.ws, (size_t)((d.M + bm - 1) / bm) * d.N * 4, d.N, st) : nullptr;
   if (d.a_kc && d.b_kc) dispatch_tile<true, true>(cfg, g, e, st);
   else if (d.a_kc && !d.b_kc) dispatch_tile<true, false>(cfg, g, e, st);
   else if (!d.a_kc && !d.b_kc) dispatch_tile<false, false>(cfg, g, e, st);
   else dispatch_tile<false, true>(cfg, g, e, st);
   int rc = hip_check("gemm_bf16");
   if (!rc && e.colsum) {  // fixed-order reduction of the per-tile column partials
-    const int bm = cfg_is_256(cfg) ? 256 : 128;
     part_reduce(g.cs_part, (d.M + bm - 1) / bm, d.N, d.N, d.N, e.colsum, nullptr, nullptr, e.colsum_accumulate,
                 nullptr, st);
     rc = hip_check("gemm_colsum_reduce");

@@ -87,15 +87,6 @@ __global__ __launch_bounds__(256) void cls_stats_kernel(ClsArgs a) {
   }
 }
 
-void cls_stats_launch(const float* logits, long ld, const int64_t* labels, int B, int C, int64_t* preds, float* conf,
-                      float* probs, long ld_probs, int64_t* confusion, int64_t* counters, hipStream_t st) {
-  ClsArgs a{};
-  a.z = logits, a.ld = ld, a.labels = (const long long*)labels, a.B = B, a.C = C, a.preds = (long long*)preds;
-  a.conf = conf, a.probs = probs, a.ldp = ld_probs, a.confusion = (unsigned long long*)confusion;
-  a.counters = (unsigned long long*)counters;
-  hipLaunchKernelGGL(cls_stats_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, st, a);
-}
-
 // ---------------------------------------------------------------- cls_report
 // One workgroup. Thread t owns classes t, t + 256, ...: integer row and column sums (exact), the class's
 // four fp64 figures, and its partial sums; thread 0 then adds the 256 partials in thread order.
@@ -134,10 +125,6 @@ __global__ __launch_bounds__(256) void cls_report_kernel(const long long* cm, in
     out[2] = n > 0 ? f1w / (double)n : 0.0;
     out[3] = (double)n;
   }
-}
-
-void cls_report_launch(const int64_t* confusion, int C, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(cls_report_kernel, dim3(1), dim3(256), 0, st, (const long long*)confusion, C, out);
 }
 
 // ---------------------------------------------------------------- token_cosine
@@ -270,8 +257,51 @@ __global__ __launch_bounds__(256) void token_cosine_fma_kernel(CosArgs a) {
   }
 }
 
-void token_cosine_launch(int dtype, const void* tokens, long ld, int B, int N, int D, float eps, float* cls_sim,
-                         long ld_cls, float* tok_sim, long ld_tok, hipStream_t st) {
+}  // namespace fer
+
+using namespace fer;
+
+// ---------------------------------------------------------------- entry points
+extern "C" int fer_cls_stats(const float* logits, int64_t ld, const int64_t* labels, int B, int C, int64_t* preds,
+                             float* conf, float* probs, int64_t ld_probs, int64_t* confusion, int64_t* counters,
+                             fer_stream_t stream) {
+  if (C < 1) return set_error("cls_stats: C must be >= 1");
+  if (!logits || !labels) return set_error("cls_stats: logits and labels are required");
+  if (ld < C) return set_error("cls_stats: the logits' row stride must be >= C");
+  if (probs && ld_probs < C) return set_error("cls_stats: the probabilities' row stride must be >= C");
+  if (B <= 0) return 0;
+  if (too_many((long)B * 64)) return set_error("cls_stats: B is too large for one launch");
+  ClsArgs a{};
+  a.z = logits, a.ld = ld, a.labels = (const long long*)labels, a.B = B, a.C = C, a.preds = (long long*)preds;
+  a.conf = conf, a.probs = probs, a.ldp = ld_probs, a.confusion = (unsigned long long*)confusion;
+  a.counters = (unsigned long long*)counters;
+  hipLaunchKernelGGL(cls_stats_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, (hipStream_t)stream, a);
+  return hip_check("cls_stats");
+}
+
+extern "C" int fer_cls_report(const int64_t* confusion, int C, double* out, fer_stream_t stream) {
+  if (C < 1) return set_error("cls_report: C must be >= 1");
+  if (!confusion || !out) return set_error("cls_report: confusion and out are required");
+  hipLaunchKernelGGL(cls_report_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const long long*)confusion, C, out);
+  return hip_check("cls_report");
+}
+
+extern "C" int fer_token_cosine(int dtype, const void* tokens, int64_t ld, int B, int N, int D, float eps,
+                                float* cls_sim, int64_t ld_cls, float* tok_sim, int64_t ld_tok, fer_stream_t stream) {
+  if (check_dtype(dtype, "token_cosine: unknown dtype")) return -1;
+  if (N < 2) return set_error("token_cosine: N must be >= 2 (row 0 and at least one more token)");
+  const int V = piece_len(dtype);
+  if (D < 1 || D % (dtype == FER_BF16 ? 32 : 4))
+    return set_error("token_cosine: D must be a positive multiple of 32 (bf16: one MFMA step) or 4 (fp32)");
+  if (!piece_ok(tokens, ld, D, V))
+    return set_error("token_cosine: tokens need 16-byte aligned rows (stride >= D, a multiple of 8 bf16 / 4 fp32)");
+  if (!cls_sim && !tok_sim) return set_error("token_cosine: no output requested");
+  if ((cls_sim && ld_cls < N - 1) || (tok_sim && ld_tok < N - 1))
+    return set_error("token_cosine: an output's row stride must be >= N - 1");
+  if (!(eps >= 0.f)) return set_error("token_cosine: eps must be >= 0");
+  if (B <= 0) return 0;
+  if (B > 65535 || N > 65535) return set_error("token_cosine: B or N is above the launch grid's limit");
+  hipStream_t st = (hipStream_t)stream;
   CosArgs a{};
   a.x = tokens, a.ld = ld, a.N = N, a.D = D, a.eps = eps, a.cls = cls_sim, a.ldc = ld_cls, a.tok = tok_sim;
   a.ldt = ld_tok;
@@ -284,6 +314,5 @@ void token_cosine_launch(int dtype, const void* tokens, long ld, int B, int N, i
     const int rows = tok_sim ? N - a.i_first : 1;
     hipLaunchKernelGGL(token_cosine_fma_kernel, dim3(ceil_div(N, 32), rows, B), dim3(256), 0, st, a);
   }
+  return hip_check("token_cosine");
 }
-
-}  // namespace fer

@@ -191,25 +191,6 @@ static long svm_forward_ws_floats(int N, int F) {
   return splits * N * SVM_P + (long)ceil_div(N, SVM_EPI_ROWS) * SVM_P;
 }
 
-void svm_forward_launch(const float* X, long ldx, const float* W, long ldw, const float* bias, int N, int F, int P,
-                        int hinge, const int64_t* labels, const int64_t* classes, const float* Cp, const float* Cn,
-                        float* Z, long ldz, float* R, long ldr, float* Dw, long ldd, float* loss, float* ws,
-                        hipStream_t st) {
-  SvmDotArgs d{};
-  d.X = X, d.W = W, d.zpart = ws, d.ldx = ldx, d.ldw = ldw, d.N = N, d.F = F, d.P = P;
-  const int splits = svm_splits(N, F, &d.chunk);
-  d.vec_x = al16(X) && ldx % 4 == 0, d.vec_w = al16(W) && ldw % 4 == 0;
-  hipLaunchKernelGGL(svm_dot_kernel, dim3(ceil_div(N, SVM_ROWS), splits), dim3(64), 0, st, d);
-  SvmEpiArgs e{};
-  e.zpart = ws, e.bias = bias, e.labels = (const long long*)labels, e.classes = (const long long*)classes;
-  e.Cp = Cp, e.Cn = Cn, e.Z = Z, e.R = R, e.Dw = Dw, e.ldz = ldz, e.ldr = ldr, e.ldd = ldd;
-  e.N = N, e.P = P, e.splits = splits, e.hinge = hinge;
-  e.losspart = ws + (long)splits * N * SVM_P;
-  const int nblk = ceil_div(N, SVM_EPI_ROWS);
-  hipLaunchKernelGGL(svm_epilogue_kernel, dim3(nblk), dim3(256), 0, st, e);
-  if (hinge) hipLaunchKernelGGL(svm_loss_kernel, dim3(1), dim3(64), 0, st, e.losspart, nblk, P, loss);
-}
-
 // ---------------------------------------------------------------- xtr
 struct SvmXtrArgs {
   const float* X;
@@ -307,8 +288,69 @@ static long svm_xtr_ws_floats(int N, int F) {
   return groups * SVM_P * (ceil_div(F, 4) * 4L) + groups * SVM_P;
 }
 
-void svm_xtr_launch(const float* X, long ldx, const float* R, long ldr, int N, int F, int P, float* G, long ldg,
-                    float* gb, float* ws, hipStream_t st) {
+static long svm_ws_bytes(int N, int F) { return 4 * std::max(svm_forward_ws_floats(N, F), svm_xtr_ws_floats(N, F)); }
+
+}  // namespace fer
+
+using namespace fer;
+
+// ---------------------------------------------------------------- entry points
+extern "C" int fer_svm_slab(void) { return FER_SVM_SLAB; }
+extern "C" int fer_svm_max_groups(void) { return FER_SVM_MAX_GROUPS; }
+extern "C" int64_t fer_svm_ws(int N, int F) { return N > 0 && F > 0 ? svm_ws_bytes(N, F) : 0; }
+
+// what both passes ask of X, the shape and the workspace; `what` is the entry's name
+static int svm_common(const char* what, const float* X, int64_t ldx, int N, int F, int P, const float* ws,
+                      int64_t ws_bytes) {
+  char msg[160];
+  const char* bad = nullptr;
+  if (F < 1) bad = "F must be >= 1";
+  else if (P < 1 || P > 8) bad = "P must be 1..8 columns per launch";
+  else if (!X || ldx < F) bad = "X is required, with a row stride >= F";
+  else if (N > 0 && (!ws || !al16(ws) || ws_bytes < svm_ws_bytes(N, F)))
+    bad = "the workspace must be 16-byte aligned and hold fer_svm_ws(N, F) bytes";
+  if (!bad) return 0;
+  snprintf(msg, sizeof(msg), "%s: %s", what, bad);
+  return set_error(msg);
+}
+
+extern "C" int fer_svm_forward(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, int N,
+                               int F, int P, int epilogue, const int64_t* labels, const int64_t* classes,
+                               const float* Cp, const float* Cn, float* Z, int64_t ldz, float* R, int64_t ldr,
+                               float* Dw, int64_t ldd, float* loss, float* ws, int64_t ws_bytes, fer_stream_t stream) {
+  if (svm_common("svm_forward", X, ldx, N, F, P, ws, ws_bytes)) return -1;
+  if (epilogue != 0 && epilogue != 1) return set_error("svm_forward: epilogue must be 0 (hinge) or 1 (scale)");
+  if (!W || ldw < F || !bias) return set_error("svm_forward: W (row stride >= F) and bias are required");
+  if (!R || ldr < P || !Dw || ldd < P) return set_error("svm_forward: R and Dw are required, with row strides >= P");
+  if (Z && ldz < P) return set_error("svm_forward: Z's row stride must be >= P");
+  if (epilogue == 0 && (!labels || !classes || !Cp || !Cn || !loss))
+    return set_error("svm_forward: the hinge epilogue needs labels, classes, Cp, Cn and loss");
+  if (N <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  SvmDotArgs d{};
+  d.X = X, d.W = W, d.zpart = ws, d.ldx = ldx, d.ldw = ldw, d.N = N, d.F = F, d.P = P;
+  const int splits = svm_splits(N, F, &d.chunk);
+  d.vec_x = al16(X) && ldx % 4 == 0, d.vec_w = al16(W) && ldw % 4 == 0;
+  hipLaunchKernelGGL(svm_dot_kernel, dim3(ceil_div(N, SVM_ROWS), splits), dim3(64), 0, st, d);
+  SvmEpiArgs e{};
+  e.zpart = ws, e.bias = bias, e.labels = (const long long*)labels, e.classes = (const long long*)classes;
+  e.Cp = Cp, e.Cn = Cn, e.Z = Z, e.R = R, e.Dw = Dw, e.ldz = ldz, e.ldr = ldr, e.ldd = ldd;
+  e.N = N, e.P = P, e.splits = splits, e.hinge = epilogue == 0;
+  e.losspart = ws + (long)splits * N * SVM_P;
+  const int nblk = ceil_div(N, SVM_EPI_ROWS);
+  hipLaunchKernelGGL(svm_epilogue_kernel, dim3(nblk), dim3(256), 0, st, e);
+  if (e.hinge) hipLaunchKernelGGL(svm_loss_kernel, dim3(1), dim3(64), 0, st, e.losspart, nblk, P, loss);
+  return hip_check("svm_forward");
+}
+
+extern "C" int fer_svm_xtr(const float* X, int64_t ldx, const float* R, int64_t ldr, int N, int F, int P, float* G,
+                           int64_t ldg, float* gb, float* ws, int64_t ws_bytes, fer_stream_t stream) {
+  if (svm_common("svm_xtr", X, ldx, N, F, P, ws, ws_bytes)) return -1;
+  if (!R || ldr < P) return set_error("svm_xtr: R is required, with a row stride >= P");
+  if (!G && !gb) return set_error("svm_xtr: no output requested");
+  if (G && ldg < F) return set_error("svm_xtr: G's row stride must be >= F");
+  if (N <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
   SvmXtrArgs a{};
   a.X = X, a.R = R, a.ldx = ldx, a.ldr = ldr, a.N = N, a.F = F, a.P = P, a.F4 = ceil_div(F, 4) * 4;
   const int groups = svm_groups(N, &a.gs);
@@ -318,8 +360,5 @@ void svm_xtr_launch(const float* X, long ldx, const float* R, long ldr, int N, i
   const long threads = (long)P * (a.F4 / 4) + P;
   hipLaunchKernelGGL(svm_xtr_reduce_kernel, dim3(blocks_for(threads)), dim3(256), 0, st, a.part, a.gbpart, groups, P, F,
                      a.F4, G, ldg, G && al16(G) && ldg % 4 == 0, gb);
+  return hip_check("svm_xtr");
 }
-
-long svm_ws_bytes(int N, int F) { return 4 * std::max(svm_forward_ws_floats(N, F), svm_xtr_ws_floats(N, F)); }
-
-}  // namespace fer

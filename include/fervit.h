@@ -158,12 +158,14 @@ int fer_layernorm_bwd(int dtype, const void* dy, int64_t lddy, const void* x, in
  * backward: lse [B*H*N] (natural log), padded to a multiple of 64 words, then -- bf16 with dropout,
  * N <= 224, dh <= 64 -- the probability-dropout keep bits, [B*H][NB][NB][32] uint32 (NB = ceil(N/32);
  * word (kb, qb, j) = bits over the 32 queries of block qb for key kb*32 + j; words of padding keys
- * kb*32 + j >= N unspecified), so the backward does not re-hash them. bf16: any N, dh <= 128, dh % 8 == 0 (persistent workgroup per CU walking the
- * (batch, head) units for N <= 256 and dh <= 64, 128-row chunks streamed through LDS otherwise). */
+ * kb*32 + j >= N unspecified), so the backward does not re-hash them. bf16: any N, dh <= 128,
+ * dh % 8 == 0. Which kernels a call runs is decided in one place, attn_plan() in csrc/attention.hip:
+ * with dh <= 64, N <= 224 runs the persistent family (workgroups walking the (batch, head) units) and
+ * 224 < N <= 256 one workgroup per unit; everything else streams 128-row chunks through LDS. */
 int64_t fer_attention_ws(int dtype, int B, int N, int H);
-/* Forward kernel for bf16, N <= 224, dh <= 64: 0 automatic (the occupancy form for N > 96 with
- * dropout on, else the persistent kernel), 1 the persistent producer / consumer kernel, 2 the occupancy form (one workgroup
- * per (batch, head), two per CU). Same results bit for bit. */
+/* Forward kernel of the persistent family: 0 automatic (the occupancy form for N > 96 with dropout on,
+ * else the persistent kernel), 1 the persistent producer / consumer kernel, 2 the occupancy form (one
+ * workgroup per (batch, head), two per CU). Same results bit for bit. */
 int fer_attention_set_fwd_kernel(int k);
 int64_t fer_attention_saved_floats(int dtype, int B, int N, int H, int dh, uint32_t drop_thresh);
 int fer_attention_fwd(int dtype, const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, float* saved,

@@ -35,7 +35,11 @@ def stream():
 
 
 def family(dtype, N, dh):
-    """The kernels the dispatcher (fer_attention_fwd / fer_attention_bwd) takes for this case."""
+    """The kernels the dispatcher (fer_attention_fwd / fer_attention_bwd) takes for this case.
+
+    The library decides this in attn_plan() (csrc/attention.hip). The rule is restated here on purpose: an
+    independent statement, so that a slip in the plan shows as a case checked against the wrong family's
+    bounds and forced kernels instead of passing unnoticed."""
     if dtype == "fp32":
         return "f32"
     if N <= 224 and dh <= 64:
@@ -246,7 +250,7 @@ def run_case(B, N, H, dh, dtype, p, ctab, styles=("normal", "peaked")):
 PERS = [(1, 2, 64, False), (2, 2, 64, False), (19, 3, 64, False), (32, 2, 64, False),      # NB 1
         (33, 2, 64, False), (64, 3, 64, False),                                              # NB 2
         (65, 2, 64, False), (96, 2, 64, False),                                              # NB 3
-        (100, 3, 64, True),                                                                  # NB 4
+        (97, 2, 64, False), (100, 3, 64, True),                                              # NB 4: occupancy form with dropout
         (150, 2, 64, False), (160, 2, 64, False),                                            # NB 5
         (161, 2, 64, False), (192, 2, 64, False),                                            # NB 6: first with the helper wave
         (197, 3, 64, True), (224, 2, 64, False)]                                             # NB 7
