@@ -54,9 +54,21 @@ class FusedAdamW(torch.optim.Optimizer):
         if flat is None:
             raise RuntimeError("FusedAdamW needs model= (a fervit FerModule) to locate the flat buffers")
         if flat is not self._flat:
+            old, m, v = self._flat, self._m, self._v
             self._flat = flat
             self._m = torch.zeros_like(flat.data)
             self._v = torch.zeros_like(flat.data)
+            self._eager = None  # the resident segment tables hold the old store's offsets
+            self._bw_tables = {}
+            if old is not None:
+                # the store was rebuilt (a real .to() / .double().float(), a re-run after a child ran
+                # alone): parameters that are still the same objects keep their moments. `old.params`
+                # keeps them alive, so an equal id is the same object.
+                with torch.no_grad():
+                    for p in old.params:
+                        if id(p) in flat.offsets and flat.grad_views[id(p)].shape == old.grad_views[id(p)].shape:
+                            flat.view(p, self._m).copy_(old.view(p, m))
+                            flat.view(p, self._v).copy_(old.view(p, v))
         return flat
 
     # ---- torch.optim.AdamW-format state (checkpoints: utils/experiment_logger.py:121-145)

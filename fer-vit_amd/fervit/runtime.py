@@ -5,8 +5,14 @@ contiguous fp32 buffer (64-element aligned offsets), its gradient in ONE fp32
 grad buffer with the same offsets, and the bf16 compute copy in ONE bf16 buffer.
 So the optimizer is one fused launch, the bf16 refresh is one cast, and DDP
 all-reduces contiguous buckets of the grad buffer with no packing copies.
-`p.data` / `p.grad` of each nn.Parameter are views into these buffers, so every
-torch API (state_dict, optimizers, clip_grad_norm_) keeps working unchanged.
+`p.data` / `p.grad` of each nn.Parameter are views into these buffers, so the torch
+APIs that go through the Parameter (state_dict, load_state_dict, optimizers, nn.init,
+clip_grad_norm_) keep working unchanged. The start of every pass (begin_pass) checks that
+each parameter still is its view: `p.data = t` is copied in and re-pointed, a replaced
+Parameter object (load_state_dict(assign=True)) or a changed dtype / device makes the owner
+rebuild the store. The one edit the host cannot see is an in-place write through `.data`
+(`p.data.mul_()`), which bumps no version counter: FerModule.fer_params_changed() marks the
+bf16 shadow stale after it.
 """
 from __future__ import annotations
 
@@ -58,8 +64,11 @@ def next_seed() -> int:
 class FlatParams:
     """Flat fp32 / grad / bf16 storage for a list of parameters (see module doc)."""
 
-    def __init__(self, params: List[torch.nn.Parameter]):
+    def __init__(self, params: List[torch.nn.Parameter], slots=()):
         self.params = list(params)
+        # (module._parameters, name, parameter) of every place the owning module holds a parameter:
+        # a slot that no longer holds its parameter means the Parameter object was replaced
+        self.slots = list(slots)
         self.offsets: Dict[int, int] = {}
         off = 0
         for p in self.params:
@@ -85,6 +94,7 @@ class FlatParams:
                 v.copy_(p.data)
                 p.data = v
         self.grad_views = {id(p): self.grad_view(p) for p in self.params}
+        self._ptrs = [p.data_ptr() for p in self.params]
 
     def view(self, p, buf=None):
         buf = self.data if buf is None else buf
@@ -112,12 +122,39 @@ class FlatParams:
             self.refresh_half_t()
         return self.half
 
-    def begin_pass(self) -> None:
+    def begin_pass(self) -> bool:
         """Start of the owning model's forward: the next bf16() compares the version signature
         (O(#params) host work) once; every other weight fetch of the pass -- and of its
-        backward -- reuses that result instead of re-summing per GEMM launch."""
+        backward -- reuses that result instead of re-summing per GEMM launch. Returns False when
+        the store no longer fits its parameters (see intact) and the owner has to rebuild it."""
         self._passes = True
         self._checked = False
+        return self.intact(adopt=True)
+
+    def intact(self, adopt: bool = False) -> bool:
+        """Every parameter's `.data` still is its view of the flat buffer and every slot of the
+        owning module still holds the Parameter object the store was built over. With `adopt`, a
+        parameter whose `.data` was re-pointed at another fp32 tensor of the same shape on the same
+        device (`p.data = t`) is copied into its view and pointed back (the shadow goes stale);
+        anything else -- another dtype, device or shape, a replaced Parameter -- returns False."""
+        for p, ptr in zip(self.params, self._ptrs):
+            if p.data_ptr() != ptr:
+                v = self.grad_views[id(p)]
+                if not adopt or p.dtype != torch.float32 or p.device != v.device or p.shape != v.shape:
+                    return False
+                v = self.view(p)
+                with torch.no_grad():
+                    v.copy_(p.data)
+                p.data = v
+                self.mark_stale()
+        for d, name, p in self.slots:
+            if d.get(name) is not p:
+                return False
+        return True
+
+    def mark_stale(self) -> None:
+        """The fp32 buffer changed in a way no version counter shows: the next bf16() casts again."""
+        self.half_version = -1
 
     def version(self) -> int:
         # in-place updates through a Parameter bump that Parameter's own counter
