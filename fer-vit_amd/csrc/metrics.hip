@@ -1,6 +1,7 @@
 // Evaluation metrics on the device (reference `eval/evaluate_model.py:135-159, 231-296`: argmax, softmax,
 // sklearn's confusion matrix and classification report on the host, torch.cosine_similarity of the final
-// tokens). Three launches, each one kernel, none reads the host or allocates, so all are capturable:
+// tokens; `sefa/verify_directions.py:48-69`: did a shift along a direction change the prediction). Four
+// launches, each one kernel, none reads the host or allocates, so all are capturable:
 //
 //   cls_stats     one wave per row of fp32 logits [B][C]: argmax by torch's CPU rule (lowest index of the
 //                 maximum, a NaN counts as the maximum, the first NaN wins), fp32 softmax, confidence, and
@@ -17,6 +18,9 @@
 //                 wave per (row i, 8 rows j). A row's squared norm is summed by the same procedure on
 //                 either side, and an element's arithmetic does not depend on which outputs were asked
 //                 for: each output requested alone or both together give the same bits.
+//   label_change  one wave per (direction k, sample i): cls_stats' argmax of the sample's base logits and of
+//                 its S shifted rows, changed = any step's prediction differs, 64-bit atomic adds into
+//                 counts[k] and step_counts[k][s].
 #include "common.h"
 #include "fervit_internal.h"
 
@@ -257,6 +261,61 @@ __global__ __launch_bounds__(256) void token_cosine_fma_kernel(CosArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- label_change
+// `sefa/verify_directions.py:48-69` on logits already computed: does any of the S shifted copies of sample i
+// along direction k change the model's prediction? shifted holds the rows in fer_latent_shift's grid order,
+// row (k*S + s)*n + i.
+struct LabelChangeArgs {
+  const float* base;
+  const float* shifted;
+  long long* preds;
+  unsigned char* changed;
+  unsigned long long* counts;
+  unsigned long long* step_counts;
+  long ldb, lds;
+  int K, S, n, C;
+};
+
+// argmax of one row by the whole wave (cls_stats' rule and reduction): the same index in every lane
+FER_DEV int wave_argmax(const float* z, int C, int lane) {
+  float bv = 0.f;
+  int bi = ARG_EMPTY;
+  for (int i = lane; i < C; i += 64) {
+    const float v = z[i];
+    if (arg_better(v, i, bv, bi)) bv = v, bi = i;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (arg_better(ov, oi, bv, bi)) bv = ov, bi = oi;
+  }
+  return bi;
+}
+
+// grid ceil(K*n / 4), 256 threads: wave = (k, i).
+__global__ __launch_bounds__(256) void label_change_kernel(LabelChangeArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= (long)a.K * a.n) return;
+  const int k = (int)(w / a.n), i = (int)(w - (long)k * a.n);
+  const int base = wave_argmax(a.base + (long)i * a.ldb, a.C, lane);
+  bool any = false;
+  for (int s = 0; s < a.S; ++s) {
+    const long ks = (long)k * a.S + s;
+    const int pred = wave_argmax(a.shifted + (ks * a.n + i) * a.lds, a.C, lane);
+    if (lane == 0) {
+      if (a.preds) a.preds[ks * a.n + i] = pred;
+      if (pred != base && a.step_counts) atomicAdd(a.step_counts + ks, 1ull);
+    }
+    any |= pred != base;
+  }
+  if (lane == 0) {
+    if (a.changed) a.changed[w] = any ? 1 : 0;
+    if (any) atomicAdd(a.counts + k, 1ull);
+  }
+}
+
 }  // namespace fer
 
 using namespace fer;
@@ -315,4 +374,21 @@ extern "C" int fer_token_cosine(int dtype, const void* tokens, int64_t ld, int B
     hipLaunchKernelGGL(token_cosine_fma_kernel, dim3(ceil_div(N, 32), rows, B), dim3(256), 0, st, a);
   }
   return hip_check("token_cosine");
+}
+
+extern "C" int fer_label_change(const float* base, int64_t ld_base, const float* shifted, int64_t ld_shifted, int K,
+                                int S, int n, int C, int64_t* preds, uint8_t* changed, int64_t* counts,
+                                int64_t* step_counts, fer_stream_t stream) {
+  if (K < 1 || S < 1) return set_error("label_change: K and S must be >= 1");
+  if (C < 1) return set_error("label_change: C must be >= 1");
+  if (!base || !shifted || !counts) return set_error("label_change: base, shifted and counts are required");
+  if (ld_base < C || ld_shifted < C) return set_error("label_change: a row stride must be >= C");
+  if (n <= 0) return 0;
+  if ((long)K * S * n > 0x7FFFFFFFL) return set_error("label_change: K * S * n is too large for one launch");
+  LabelChangeArgs a{};
+  a.base = base, a.ldb = ld_base, a.shifted = shifted, a.lds = ld_shifted, a.K = K, a.S = S, a.n = n, a.C = C;
+  a.preds = (long long*)preds, a.changed = changed, a.counts = (unsigned long long*)counts;
+  a.step_counts = (unsigned long long*)step_counts;
+  hipLaunchKernelGGL(label_change_kernel, dim3(ceil_div((long)K * n, 4)), dim3(256), 0, (hipStream_t)stream, a);
+  return hip_check("label_change");
 }

@@ -327,3 +327,33 @@ extern "C" int fer_latent_augment(float* x, int64_t B, int LD, float noise_std, 
                      noise_std, scale_lo, scale_hi, mask_prob, seed);
   return hip_check("latent_augment");
 }
+
+// ------------------------------------------------------------------ direction draw
+// The per-sample draw behind direction augmentation (fer_latent_shift in choice mode): sample i is left
+// unchanged (choice -1) with probability p_keep, else takes one of n_choices (direction, step) pairs with
+// equal probability. That is the per-sample distribution of drawing uniformly from the reference's expanded
+// directory (`data/augment_latents.py:47-71`: 1 original + K*S variants per sample) when p_keep =
+// 1 / (1 + K*S). Two hashes per sample, counters 2i and 2i + 1; the pair index is the high word of
+// hash * n_choices (integers only: a host replica gives the same values).
+constexpr uint64_t DIR_XOR = 0xD1B54A32D192ED03ull;
+__global__ void latent_dir_draw_kernel(int* __restrict__ choice, long n, uint32_t n_choices, float p_keep,
+                                       uint64_t seed) {
+  seed = step_seed(seed) ^ DIR_XOR;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
+    const uint32_t e = (uint32_t)i;
+    const float u = u01(fer_hash(seed, 2u * e));
+    choice[i] = u <= p_keep ? -1 : (int)(((uint64_t)fer_hash(seed, 2u * e + 1u) * n_choices) >> 32);
+  }
+}
+
+extern "C" int fer_latent_dir_draw(int32_t* choice, int64_t n, int n_choices, float p_keep, uint64_t seed,
+                                   fer_stream_t stream) {
+  if (n_choices < 1) return set_error("latent_dir_draw: n_choices must be >= 1");
+  if (!(p_keep >= 0.f && p_keep <= 1.f)) return set_error("latent_dir_draw: p_keep must be in [0, 1]");
+  if (n <= 0) return 0;
+  if (!choice) return set_error("latent_dir_draw: choice is required");
+  if (n > 0x7FFFFFFFL) return set_error("latent_dir_draw: more than 2^31 samples per call");
+  hipLaunchKernelGGL(latent_dir_draw_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, choice, (long)n,
+                     (uint32_t)n_choices, p_keep, seed);
+  return hip_check("latent_dir_draw");
+}

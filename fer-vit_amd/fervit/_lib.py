@@ -135,6 +135,9 @@ SIGNATURES = {
     "fer_adamw": (i32, [fp, fp, fp, fp, vp, vp, i32, i64, f32, fp, vp, vp]),
     "fer_set_step_counter": (i32, [vp]),
     "fer_latent_augment": (i32, [fp, i64, i32, f32, f32, f32, f32, u64, vp]),
+    "fer_latent_shift": (i32, [fp, i64, fp, i32, fp, vp, fp, i64, i64, i32, i32, i32, i32, vp]),
+    "fer_latent_dir_draw": (i32, [vp, i64, i32, f32, u64, vp]),
+    "fer_label_change": (i32, [fp, i64, fp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "fer_step_advance": (i32, [vp, vp]),
     "fer_transpose_bf16_segments": (i32, [vp, vp, vp, i32, i64, vp]),
     "fer_image_aug_draw": (i32, [fp, i32, i32, vp, u64, vp]),

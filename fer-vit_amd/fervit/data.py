@@ -14,7 +14,12 @@ per GPU that is the bottleneck, so here:
   * `PackedLatentLoader` yields device batches: a background thread gathers batch k+1 with
     native threads into pinned memory while the GPU runs batch k, the H2D copy runs on a side
     stream, and LatentAugment (noise / per-sample scale / feature mask) runs on device
-    (`fer_latent_augment`) instead of per sample on the host.
+    (`fer_latent_augment`) instead of per sample on the host. With `augment["directions"]` each
+    sample is first pushed along a drawn (direction, step) pair or left as it is
+    (`fer_latent_dir_draw`, `fer_latent_shift`): the reference's expanded directory
+    (`data/augment_latents.py`) sampled uniformly, without writing it;
+  * `augment_shard(src, dst, directions, direction_indices, step_sizes)` writes that expanded
+    set as one shard where a file is wanted.
 """
 from __future__ import annotations
 
@@ -132,6 +137,64 @@ def write_shard(out_path: str, latents: np.ndarray, labels: np.ndarray, img_path
         f.write(blob)
 
 
+def augment_shard(src_shard: str, dst_shard: str, directions, direction_indices: Sequence[int],
+                  step_sizes: Sequence[float] = (-2.0, -1.0, 1.0, 2.0), block: int = 256) -> int:
+    """The reference's expanded directory (`data/augment_latents.py:8-77`) as one packed shard: the n samples
+    of `src_shard` as they are, then for each sample, in order, its variants along directions[d] for d in
+    `direction_indices` (outer) and every step of `step_sizes` (inner), n * (1 + K' * S) samples in all. A
+    variant carries its sample's label and image path. `directions` is [K, D] (broadcast over the layers) or
+    [K, L, D]. The variants of `block` samples come from one device launch (`fer_latent_shift`): bit-equal to
+    `w + step * direction` in torch on the CPU. Returns the count written."""
+    from . import ops
+
+    ds = PackedLatentDataset(src_shard)
+    try:
+        n, Lx, Dx = len(ds), ds.L, ds.D
+        idx = [int(i) for i in direction_indices]
+        K, S = len(idx), len(step_sizes)
+        per = K * S
+        total = n * (1 + per)
+        labels_off = 64
+        latents_off = (labels_off + 4 * total + 4095) // 4096 * 4096
+        nbytes = total * Lx * Dx * 4
+        paths = ds.img_paths()
+        blob = b"\0".join(p.encode() for p in list(paths) + [p for p in paths for _ in range(per)]) \
+            if any(paths) else b""
+        tmp = dst_shard + ".tmp"
+        with open(tmp, "wb") as f:
+            f.truncate(latents_off + nbytes)
+        mm = np.memmap(tmp, dtype=np.uint8, mode="r+")
+        lab = np.ndarray((total,), dtype=np.int32, buffer=mm, offset=labels_off)
+        lat = np.ndarray((total, Lx, Dx), dtype=np.float32, buffer=mm, offset=latents_off)
+        lab[:n] = ds.labels
+        lab[n:] = np.repeat(ds.labels, per)
+        if per:
+            dirs = torch.as_tensor(np.asarray(directions)[idx], dtype=torch.float32).cuda().contiguous()
+            steps = torch.tensor([float(s) for s in step_sizes], dtype=torch.float32, device="cuda")
+        x = torch.empty(min(block, max(n, 1)), Lx, Dx, dtype=torch.float32)
+        for i0 in range(0, n, block):
+            nb = min(block, n - i0)
+            ds.gather(np.arange(i0, i0 + nb), x)
+            lat[i0:i0 + nb] = x[:nb].numpy()
+            if per:
+                v = ops.latent_shift(x[:nb].cuda(), dirs, steps)  # rows (direction, step, sample)
+                v = v.reshape(K, S, nb, Lx, Dx).permute(2, 0, 1, 3, 4).contiguous().cpu()
+                lat[n + i0 * per:n + (i0 + nb) * per] = v.reshape(nb * per, Lx, Dx).numpy()
+        mm.flush()
+        del lab, lat, mm
+        with open(tmp, "r+b") as f:
+            f.seek(latents_off + nbytes)
+            f.write(blob)
+            f.seek(0)
+            hdr = MAGIC + np.array([total], dtype=np.uint64).tobytes() + np.array([Lx, Dx, 0, 0], dtype=np.uint32).tobytes()
+            hdr += np.array([labels_off, latents_off, latents_off + nbytes, len(blob)], dtype=np.uint64).tobytes()
+            f.write(hdr)
+        os.replace(tmp, dst_shard)
+        return total
+    finally:
+        ds.close()
+
+
 # ------------------------------------------------------------------ dataset
 class PackedLatentDataset(torch.utils.data.Dataset):
     """LatentFERDataset over a packed shard: `ds[i] -> (latent fp32 [L, D], label)`."""
@@ -203,6 +266,12 @@ class PackedLatentLoader:
     epoch's order like DistributedSampler (padded to a multiple of world_size); `indices`
     restricts to a subset (e.g. the class-balanced fraction of `train_latent_vit_v2.py:42-76`).
     augment: dict(noise_std=, scale_range=(lo, hi), mask_prob=) -> LatentAugment on device.
+    With directions= (fp32 [K, D], broadcast over the layers, or [K, L, D]) in that dict, each sample is first
+    left unchanged with probability dir_keep, else pushed along one of the K directions by one of dir_steps
+    (default (-2, -1, 1, 2)), every pair equally likely. dir_keep defaults to 1 / (1 + K * S), the share of
+    originals in the reference's expanded directory (`data/augment_latents.py`), so a sample is distributed as
+    one read uniformly from that directory; LatentAugment then runs on the result, as the reference's
+    transform runs on the expanded files.
     device=None yields pinned CPU tensors (no GPU needed)."""
 
     def __init__(self, dataset: PackedLatentDataset, batch_size: int, shuffle: bool = True, drop_last: bool = False,
@@ -216,6 +285,20 @@ class PackedLatentLoader:
         self.rank, self.world = int(rank), int(world_size)
         self.threads = threads
         self.augment = augment
+        self._dirs = None
+        if augment and augment.get("directions") is not None:
+            if self.device is None or self.device.type != "cuda":
+                raise ValueError("PackedLatentLoader: direction augmentation runs on the device (device=None given)")
+            d = torch.as_tensor(augment["directions"]).to(device=self.device, dtype=torch.float32).contiguous()
+            if d.dim() not in (2, 3) or d.shape[0] < 1 or tuple(d.shape[1:]) not in ((dataset.D,), (dataset.L, dataset.D)):
+                raise ValueError(f"PackedLatentLoader: directions must be [K, {dataset.D}] or "
+                                 f"[K, {dataset.L}, {dataset.D}], got {tuple(d.shape)}")
+            steps = [float(s) for s in augment.get("dir_steps", (-2.0, -1.0, 1.0, 2.0))]
+            if not steps:
+                raise ValueError("PackedLatentLoader: dir_steps is empty")
+            keep = augment.get("dir_keep")
+            keep = 1.0 / (1 + d.shape[0] * len(steps)) if keep is None else float(keep)
+            self._dirs = (d, torch.tensor(steps, dtype=torch.float32, device=self.device), keep)
         self.epoch = 0
         pin = self.device is not None and self.device.type == "cuda"
         shape = (self.B, dataset.L, dataset.D)
@@ -311,6 +394,13 @@ class PackedLatentLoader:
         a = self.augment
         lo, hi = a.get("scale_range") or (1.0, 1.0)
         seed = (self.seed * 0x9E3779B97F4A7C15 + (self.epoch << 32) + k * 0xBF58476D1CE4E5B9 + self.rank) % (1 << 64)
+        if self._dirs is not None:
+            # the draw's stream is a sub-seed of the batch seed (the kernel xors its own constant into it)
+            d, steps, keep = self._dirs
+            choice = ops.latent_dir_draw(x.shape[0], d.shape[0] * steps.shape[0], keep, seed, x.device)
+            ops.latent_shift(x, d, steps, choice=choice, out=x)
+            if not (a.get("noise_std") or a.get("mask_prob") or (lo, hi) != (1.0, 1.0)):
+                return
         check(lib().fer_latent_augment(x.data_ptr(), x.shape[0], x.shape[1] * x.shape[2], float(a.get("noise_std", 0.0)),
                                        float(lo), float(hi), float(a.get("mask_prob", 0.0)), seed, ops.stream()),
               "latent_augment")

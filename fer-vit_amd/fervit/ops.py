@@ -386,6 +386,97 @@ def token_cosine(tokens, eps=1e-8, want_cls=True, want_tok=True):
     return cls, tok
 
 
+def label_change(base, shifted, K, S, *, counts=None, step_counts=None, want_preds=True, want_changed=True):
+    """One fer_label_change launch: base fp32 [n, C] and shifted fp32 [K*S*n, C] logits (unit column stride,
+    shifted in latent_shift's grid order) -> (preds int64 [K, S, n], changed uint8 [K, n], counts int64 [K],
+    step_counts int64 [K, S]); None for preds / changed not asked for. `counts` and `step_counts` are
+    accumulated in place when given (contiguous), else start from zero. No host sync."""
+    _dev(base)
+    _dev(shifted)
+    for name, t in (("base", base), ("shifted", shifted)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 1 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"label_change: {name} must be fp32 [rows, C >= 1] with unit column stride")
+    n, C = base.shape
+    if K < 1 or S < 1 or tuple(shifted.shape) != (K * S * n, C):
+        raise ValueError("label_change: shifted must be [K * S * n, C] with K, S >= 1")
+    dev = base.device
+    if counts is None:
+        counts = torch.zeros(K, dtype=torch.int64, device=dev)
+    elif not _out("label_change: counts", counts, base, (K,), torch.int64).is_contiguous():
+        raise ValueError("label_change: counts must be contiguous")
+    if step_counts is None:
+        step_counts = torch.zeros(K, S, dtype=torch.int64, device=dev)
+    elif not _out("label_change: step_counts", step_counts, base, (K, S), torch.int64).is_contiguous():
+        raise ValueError("label_change: step_counts must be contiguous")
+    preds = torch.empty(K, S, n, dtype=torch.int64, device=dev) if want_preds else None
+    changed = torch.empty(K, n, dtype=torch.uint8, device=dev) if want_changed else None
+    if n:
+        check(lib().fer_label_change(base.data_ptr(), base.stride(0) if n > 1 else max(C, base.stride(0)),
+                                     shifted.data_ptr(), max(C, shifted.stride(0)), K, S, n, C, ptr(preds),
+                                     ptr(changed), counts.data_ptr(), step_counts.data_ptr(), stream()),
+              "label_change")
+    return preds, changed, counts, step_counts
+
+
+# ------------------------------------------------------------------ latent directions
+def _latents(name, t):
+    """fp32 [n, L, D] with contiguous samples (the sample stride is free, at least L * D)."""
+    _dev(t)
+    if t.dtype != torch.float32 or t.dim() != 3 or t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError(f"latent_shift: {name} must be fp32 [n, L, D]")
+    n, L, D = t.shape
+    if (D > 1 and t.stride(2) != 1) or (L > 1 and t.stride(1) != D) or (n > 1 and t.stride(0) < L * D):
+        raise ValueError(f"latent_shift: {name} needs contiguous [L, D] samples at a stride of at least L * D")
+    return L * D if n <= 1 else t.stride(0)
+
+
+def latent_shift(x, directions, steps, choice=None, out=None):
+    """fer_latent_shift: x fp32 [n, L, D] pushed along `directions` (fp32 [K, D], broadcast over the layers, or
+    [K, L, D]) by `steps` (fp32 [S] on the device). choice=None: every (direction, step) variant,
+    out [K*S*n, L, D] in (direction, step, sample) order. choice int32 [n]: row i takes pair choice[i] = k*S + s,
+    or stays bit for bit when the value is outside [0, K*S); out [n, L, D], and out=x shifts in place.
+    The product and the sum are rounded separately: bit-equal to torch's `x + step * d` on the CPU."""
+    ldx = _latents("x", x)
+    n, L, D = x.shape
+    for t in (directions, steps):
+        _dev(t)
+    if directions.dtype != torch.float32 or not directions.is_contiguous() or directions.shape[0] < 1 or \
+            tuple(directions.shape[1:]) not in ((D,), (L, D)):
+        raise ValueError("latent_shift: directions must be contiguous fp32 [K, D] or [K, L, D], K >= 1")
+    K, dir_layers = directions.shape[0], (1 if directions.dim() == 2 else L)
+    if steps.dtype != torch.float32 or steps.dim() != 1 or steps.shape[0] < 1 or not steps.is_contiguous():
+        raise ValueError("latent_shift: steps must be a contiguous fp32 [S] tensor, S >= 1")
+    S = steps.shape[0]
+    if choice is not None:
+        _dev(choice)
+        if choice.dtype != torch.int32 or tuple(choice.shape) != (n,) or not choice.is_contiguous():
+            raise ValueError("latent_shift: choice must be a contiguous int32 [n] tensor")
+    rows = n if choice is not None else K * S * n
+    if out is None:
+        out = torch.empty(rows, L, D, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (rows, L, D) or out.device != x.device:
+        raise ValueError(f"latent_shift: out must be [{rows}, {L}, {D}] on x's device")
+    ldo = _latents("out", out)
+    if choice is None and rows and out.untyped_storage().data_ptr() == x.untyped_storage().data_ptr():
+        raise ValueError("latent_shift: in place only with a choice")
+    check(lib().fer_latent_shift(x.data_ptr(), ldx, directions.data_ptr(), dir_layers, steps.data_ptr(), ptr(choice),
+                                 out.data_ptr(), ldo, n, K, S, L, D, stream()), "latent_shift")
+    return out
+
+
+def latent_dir_draw(n, n_choices, p_keep, seed, device="cuda", out=None):
+    """fer_latent_dir_draw: int32 [n] on `device`, -1 (unchanged) with probability p_keep, else uniform over
+    [0, n_choices): the `choice` of latent_shift."""
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (n,) or not out.is_contiguous():
+        raise ValueError("latent_dir_draw: out must be a contiguous int32 [n] tensor")
+    _dev(out)
+    check(lib().fer_latent_dir_draw(out.data_ptr(), n, int(n_choices), float(p_keep), seed64(seed), stream()),
+          "latent_dir_draw")
+    return out
+
+
 # ------------------------------------------------------------------ linear-SVM passes
 SVM_COLUMNS = 8  # columns (one-vs-rest problems) per launch
 

@@ -584,6 +584,42 @@ int fer_transpose_bf16_segments(const void* src, void* dst, const int64_t* segs,
 int fer_latent_augment(float* x, int64_t B, int LD, float noise_std, float scale_lo, float scale_hi,
                        float mask_prob, uint64_t seed, fer_stream_t stream);
 
+/* Latents pushed along direction vectors (`sefa/verify_directions.py:57-58`, `data/augment_latents.py:56`:
+ * w + step * direction), csrc/latent_dirs.hip. Everything fp32:
+ *   out[r][l][:] = x[src(r)][l][:] + steps[c % S] * dirs[c / S][l or 0][:]
+ * x [n][L][D] at sample stride ldx, out at sample stride ldo (both >= L*D, in floats), steps [S],
+ * dirs [K][D] (dir_layers = 1: one vector broadcast over the layers, a SeFa direction) or [K][L][D]
+ * (dir_layers = L: a w+ direction), contiguous. The product and the sum are rounded separately (no FMA):
+ * bit-equal to torch's `x + step * d` on the CPU.
+ *   choice == NULL (grid mode): out holds K*S*n rows, row r = (k*S + s)*n + i is sample i shifted by pair
+ *     c = k*S + s. out must not overlap x.
+ *   choice != NULL (choice mode): int32 [n], out holds n rows, src(r) = r, c = choice[r]; a value outside
+ *     [0, K*S) copies the row bit for bit and reads neither dirs nor steps. out == x is allowed.
+ * 16-byte loads and stores when D % 4 == 0, both strides are multiples of 4 and x, out and dirs are 16-byte
+ * aligned; element by element otherwise, same bits. K < 1, S < 1, dir_layers outside {1, L}, a stride below
+ * L*D or more than 2^31 - 1 output elements: a negative code, a message, nothing launched. n <= 0 is a no-op. */
+int fer_latent_shift(const float* x, int64_t ldx, const float* dirs, int dir_layers, const float* steps,
+                     const int32_t* choice, float* out, int64_t ldo, int64_t n, int K, int S, int L, int D,
+                     fer_stream_t stream);
+/* The per-sample draw for fer_latent_shift's choice mode: choice[i] = -1 (unchanged) when
+ * u01(hash(seed', 2i)) <= p_keep, else floor(hash(seed', 2i + 1) * n_choices / 2^32), uniform over
+ * [0, n_choices). seed' = the seed mixed with the step counter below (when set) xor a constant of this
+ * entry point, so the stream differs from fer_latent_augment's under the same seed. p_keep = 1 / (1 + K*S) is
+ * the share of originals in the reference's expanded directory (`data/augment_latents.py:47-71`). */
+int fer_latent_dir_draw(int32_t* choice, int64_t n, int n_choices, float p_keep, uint64_t seed, fer_stream_t stream);
+/* `sefa/verify_directions.py:48-69` on logits: base fp32 [n][C] (row stride ld_base), shifted fp32
+ * [K*S*n][C] (row stride ld_shifted) in fer_latent_shift's grid order. One wave per (k, i): argmax by
+ * fer_cls_stats' rule of the base row and of the S shifted rows, changed = any of them differs from the base.
+ *   preds int64 [K][S][n]   the shifted rows' predictions (optional)
+ *   changed uint8 [K][n]    0 / 1 (optional)
+ *   counts int64 [K]        ACCUMULATED: samples of direction k whose label changed (required)
+ *   step_counts int64 [K][S] ACCUMULATED: per step, samples whose prediction differs from the base (optional)
+ * 64-bit integer atomic adds: any order, same bits. A caller chunks over directions or over samples by
+ * offsetting the pointers. No host read: capturable. n <= 0 is a no-op. */
+int fer_label_change(const float* base, int64_t ld_base, const float* shifted, int64_t ld_shifted, int K, int S,
+                     int n, int C, int64_t* preds, uint8_t* changed, int64_t* counts, int64_t* step_counts,
+                     fer_stream_t stream);
+
 /* ImageViT input transforms (`data/image_dataset.py:139-173`, torchvision on PIL images) on the
  * device, SURVEY §8(f) row 4. Sources: B decoded uint8 HWC images (C = 1 or 3) packed in one
  * device buffer, image b at src + offsets[b], hwc[3b..3b+2] = H, W, C. Output fp32 NCHW
