@@ -24,6 +24,19 @@ def fer_hash(seed: int, pair: np.ndarray) -> np.ndarray:
     return x
 
 
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def step_seed(seed: int, counter: int) -> int:
+    """csrc/step_seed.h step_seed with a device counter registered and holding `counter`: the splitmix64
+    finaliser of seed ^ (counter * 0x9E3779B97F4A7C15), everything in 64 bits. A counter of 0 still mixes (the
+    finaliser of the seed itself); only an unregistered counter leaves the seed as it is."""
+    z = ((seed & _M64) ^ ((counter & _M64) * 0x9E3779B97F4A7C15)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
 def thresh(p: float) -> int:
     return max(1, min(65535, int(round(p * 65536.0))))
 

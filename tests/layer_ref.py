@@ -20,7 +20,7 @@ from typing import Tuple
 import torch
 
 from attention_ref import attn_keep
-from dropmask import keep_mask, keep_mask_torch
+from dropmask import keep_mask, keep_mask_torch, step_seed
 from elemwise import BF_ROUND, assert_close, measure_c
 from fervit import runtime
 
@@ -362,9 +362,25 @@ def case_masks(case, pas, device="cpu"):
         s = site_seeds(case.seed, 4 * (pas + 1))[4 * pas:]
         return layer_masks(s, B, N, D, H, F, p, device)
     per = 1 + 4 * IMG["depth"]
-    s = site_seeds(case.seed, per * (pas + 1))[per * pas:]
+    return image_vit_masks(case, site_seeds(case.seed, per * (pas + 1))[per * pas:], device)
+
+
+def image_vit_masks(case, s, device="cpu"):
+    """[tokens, layer 0, ...] masks of an image_vit case from the 1 + 4 * depth seeds of one pass, in draw order."""
+    B, N, D, H, F, p = case.B, case.N, case.D, case.H, case.F, case.p
+    assert len(s) == 1 + 4 * IMG["depth"]
     return [tokens_mask(s[0], B, N, D, p, device)] + [layer_masks(s[1 + 4 * i:5 + 4 * i], B, N, D, H, F, p, device)
                                                        for i in range(IMG["depth"])]
+
+
+def replay_masks(case, drawn, replay, device="cpu"):
+    """The masks of replay `replay` (1, 2, ...) of an image_vit step captured by fervit.graph.StepGraph after
+    `drawn` host seeds (those of the eager warm-up steps): the captured launches keep the host seeds drawn + 1 ..
+    drawn + 9, and every kernel mixes the device step counter into its seed (csrc/step_seed.h). The counter is
+    advanced by the first node of the graph, so replay r runs with the counter at r."""
+    per = 1 + 4 * IMG["depth"]
+    host = site_seeds(case.seed, drawn + per)[drawn:]
+    return image_vit_masks(case, [step_seed(h, replay) for h in host], device)
 
 
 def forward(case, x, P, masks, num, eps=None):
@@ -433,6 +449,22 @@ def c_table(kind, act="gelu"):
         for dtype in case.dtypes:
             ps[dtype] += pairs(run_case(case, emulate(dtype)), ref, dtype)
     return {dtype: measure_c(f"layer {kind} {act}", dtype, ps[dtype]) for dtype in ps}
+
+
+@functools.lru_cache(maxsize=None)
+def replay_c_table(case, drawn, replays):
+    """{dtype: (c of the replayed step, its own CPU measurement)} for tests/test_gpu_graph_dropout.py: c_table of
+    the kind (measured with the eager masks), or, where the same CPU measurement with the masks of replays 1 ..
+    `replays` (replay_masks) comes out larger, that one (measure_c: x 4, floor 16). Never from a kernel."""
+    table = c_table(case.kind, case.act)
+    ps = {dtype: [] for dtype in case.dtypes}
+    for r in range(1, replays + 1):
+        masks_of = lambda c, pas, device, r=r: replay_masks(c, drawn, r, device)  # noqa: E731
+        ref = run_case(case, REF, masks_of=masks_of, accumulate=False)
+        for dtype in case.dtypes:
+            ps[dtype] += pairs(run_case(case, emulate(dtype), masks_of=masks_of, accumulate=False), ref, dtype)
+    own = {dtype: measure_c(f"layer {case.kind} replayed", dtype, ps[dtype]) for dtype in ps}
+    return {dtype: (max(table[dtype], own[dtype]), own[dtype]) for dtype in ps}
 
 
 def compare(tag, got, ref, c, dtype, worst=None):
