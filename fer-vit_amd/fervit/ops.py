@@ -1114,3 +1114,34 @@ def highway_bwd(dy, pn, pl, pg, mean, rstd, gamma, beta, train, act="lrelu", dga
                                 dp[2].data_ptr(), Cc, B * Cc if G > 1 else 0, ptr(dgamma), ptr(dbeta),
                                 int(accumulate), int(skip_mask), G, B, Cc, stream()), "highway_bwd")
     return dp
+
+
+# ------------------------------------------------------------------ low-latency inference (csrc/skinny.hip)
+def skinny_linear(x, w, bias=None, *, act="none", ln_a=None, res=None, ln_res=None, out=None):
+    """One fer_skinny_linear launch for M <= 64 bf16 rows: out = act(x' w^T + bias) + res', with
+    x' = x or LayerNorm(x) (ln_a = (gamma, beta, eps), normalised on load) and res' = nothing, res or
+    LayerNorm(res) (ln_res = (gamma, beta, eps), added in fp32). x [M, K], w [N, K], res / out [M, N] bf16 with
+    unit column stride; bias, gamma, beta fp32. act: "none", "relu" or "gelu". The library checks the contract
+    (M, multiples of 8, strides, alignment) and the call raises FerError on a violation."""
+    _dev(x)
+    if act not in ("none", "relu", "gelu"):
+        raise ValueError(f"skinny_linear: unknown activation {act!r}")
+    M, K = x.shape
+    N = w.shape[0]
+    for name, t in (("x", x), ("w", w), ("res", res), ("out", out)):
+        if t is not None and (t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1):
+            raise TypeError(f"skinny_linear: {name} must be a bf16 [rows, cols] tensor with unit column stride")
+    for name, t in (("bias", bias), *((n, t) for ln, n in ((ln_a, "ln_a"), (ln_res, "ln_res")) if ln for t in ln[:2])):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(f"skinny_linear: {name} must be contiguous fp32")
+    if w.shape[1] != K or (res is not None and tuple(res.shape) != (M, N)) or (ln_res is not None and res is None):
+        raise ValueError("skinny_linear: x [M, K], w [N, K], res [M, N]; ln_res needs res")
+    out = _alloc(out, x, (M, N))
+    if tuple(out.shape) != (M, N):
+        raise ValueError("skinny_linear: out must be [M, N]")
+    ga, ba, ea = (ln_a[0], ln_a[1], float(ln_a[2])) if ln_a else (None, None, 0.0)
+    gr, br, er = (ln_res[0], ln_res[1], float(ln_res[2])) if ln_res else (None, None, 0.0)
+    check(lib().fer_skinny_linear(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), ptr(bias), ACT[act], ptr(ga),
+                                  ptr(ba), ea, *_row(res, N), ptr(gr), ptr(br), er, out.data_ptr(), out.stride(0),
+                                  M, N, K, stream()), "skinny_linear")
+    return out

@@ -653,6 +653,25 @@ int fer_sumsq(const float* x, int64_t n, float* out, float* ws, int64_t ws_bytes
 /* clip coefficient: coef = min(1, max_norm / (sqrt(sumsq*sq_scale) + 1e-6)) (torch clip_grad_norm_). */
 int fer_clip_coef(const float* sumsq, float sq_scale, float max_norm, float* coef, fer_stream_t stream);
 
+/* ---- Low-latency inference (csrc/skinny.hip; fervit/infer.py InferenceSession). One launch, bf16, M <= 64 rows:
+ *   out[M][N] = act(A' W^T + bias) + R'
+ *   A' = A, or LN(A; gamma_a, beta_a, eps_a) when gamma_a is given (normalised on load, row width K)
+ *   R' = nothing (res NULL), res, or LN(res; gamma_r, beta_r, eps_r) when gamma_r is given (row width N)
+ *   act = FER_ACT_NONE_, FER_ACT_GELU_ (erf) or FER_ACT_RELU_
+ * A [M][lda], W [N][ldw] (K-contiguous, nn.Linear's layout), res [M][ldr] and out [M][ldc] are bf16; bias,
+ * gamma and beta are fp32. Accumulation is fp32; the LayerNorm statistics are fp32, taken from the stored bf16
+ * values (biased variance); A' is rounded to bf16 as the matrix operand, LN(res) is added in fp32 without
+ * being rounded to bf16 first. A post-norm encoder layer is five launches with both LayerNorms folded into
+ * their consumers.
+ * Contract: 1 <= M <= 64; K % 8 == 0 and N % 8 == 0; every ld covers its row and is a multiple of 8; every
+ * base pointer is 16-byte aligned; gamma and beta come in pairs. Anything else returns a negative code and
+ * sets fer_last_error before any launch. N / 16 workgroups that never communicate: the result is
+ * deterministic, and row m of the output does not depend on M or on the other rows. out may alias nothing. */
+int fer_skinny_linear(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, int act,
+                      const float* gamma_a, const float* beta_a, float eps_a, const void* res, int64_t ldr,
+                      const float* gamma_r, const float* beta_r, float eps_r, void* out, int64_t ldc, int M, int N,
+                      int K, fer_stream_t stream);
+
 const char* fer_last_error(void);
 const char* fer_version(void);
 
