@@ -145,6 +145,7 @@ SIGNATURES = {
     "fer_sumsq": (i32, [fp, i64, fp, fp, i64, vp]),
     "fer_clip_coef": (i32, [fp, f32, f32, fp, vp]),
     "fer_skinny_linear": (i32, [vp, i64, vp, i64, fp, i32, fp, fp, f32, vp, i64, fp, fp, f32, vp, i64, i32, i32, i32, vp]),
+    "fer_skinny_adapter": (i32, [vp, i64, vp, i64, fp, vp, i64, fp, fp, vp, i64, i32, i32, i32, vp]),
     "fer_last_error": (C.c_char_p, []),
     "fer_version": (C.c_char_p, []),
 }

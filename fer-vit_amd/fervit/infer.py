@@ -25,8 +25,20 @@ Two forward plans:
         5. z   = skinny(g) + LN1(y)
     then fer_layernorm_fwd (the last LN2) on the B CLS rows only and fer_head_fwd. Numerically it differs from
     the eager bf16 forward only in where bf16 roundings fall (the residual operand LN(.) stays fp32).
-  skinny="auto" takes the skinny plan where it applies and B * N <= SKINNY_AUTO_MAX_ROWS, "on" requires it
-  (RuntimeError outside its contract), "off" always captures the model's own forward.
+    The pre-norm family (HybridLatentViT: timm Blocks with an optional AdapterModule after each; ExpressionAwareViT:
+    the model's own decomposer call and w+ prologue, then the hybrid) runs the same launches in pre-norm order,
+    x being the block's input:
+        1. qkv = skinny(norm1-on-load(x))
+        2. o   = fer_attention_fwd(qkv)
+        3. x1  = skinny(o) + x
+        4. g   = gelu(skinny(norm2-on-load(x1)))
+        5. x2  = skinny(g) + x1
+        6. x3  = x2 + alpha * adapter(x2)                  (csrc/skinny_adapter.hip fer_skinny_adapter; alpha is
+                                                            read on the device), where the model has adapters
+    then fer_head_fwd on the B CLS rows (row stride N; it applies the head's LayerNorm itself).
+  skinny="auto" takes the skinny plan where it applies and B * N <= SKINNY_AUTO_MAX_ROWS (post-norm models) or
+  SKINNY_AUTO_MAX_ROWS_PRENORM (pre-norm family), "on" requires it (RuntimeError outside its contract), "off"
+  always captures the model's own forward.
 
 The capture is a single stream without forks (the weight-gradient stream is a backward-only device), warmed up
 eagerly on that stream first so that every library workspace is sized before capture.
@@ -47,7 +59,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import layers, ops
-from .blocks import Encoder, EncoderLayer
+from .blocks import AdapterModule, Block, Encoder, EncoderLayer
 from .layers import LatentTokensFn, LayerCfg, PatchTokensFn
 from .module import FerModule
 
@@ -61,6 +73,30 @@ SKINNY_MAX_ROWS = 64  # fer_skinny_linear's M cap
 #   57 rows (B = 3): depth 2 140.8 vs 144.2, depth 6 408.7 vs 385.0   -> loses per layer: graph-only
 SKINNY_AUTO_MAX_ROWS = 38
 
+# The same cut-off for the pre-norm family (HybridLatentViT, ExpressionAwareViT; 12 blocks, six launches per block
+# with adapters), at the tiny (D 192) and the base (D 768, BASELINE config 4) size, adapters of width 64
+# (tools/infer_latency_bench.py --family prenorm, profiles/infer_latency_prenorm.json; medians in us, skinny vs
+# graph-only, the arms' spreads in brackets):
+#   19 rows (B = 1): tiny 376.1 [0.5] vs 717.5 [8.6], base  676.0 [1.3] vs 1198.6 [80.5]
+#   38 rows (B = 2): tiny 425.1 [0.2] vs 749.8 [8.3], base  870.6 [1.3] vs 1165.2 [31.5]
+#   57 rows (B = 3): tiny 488.3 [0.5] vs 767.7 [7.1], base 1022.5 [1.8] vs 1208.1 [8.0]
+#   37 rows (tiny concat, B = 1): 474.9 [0.5] vs 827.4 [6.7]
+# The skinny plan wins at every measured row count; 57 is the largest one measured (58 - 64 rows: unmeasured,
+# left graph-only).
+SKINNY_AUTO_MAX_ROWS_PRENORM = 57
+
+ADAPTER_MAX_WIDTH = 128  # fer_skinny_adapter's R cap
+
+
+def _is_hybrid(m) -> bool:
+    """HybridLatentViT's parts: input_proj, cls_token, pos_embed, a transformer of fervit Blocks, optional
+    adapters, head = LayerNorm, Dropout, Linear."""
+    tr, head = getattr(m, "transformer", None), getattr(m, "head", None)
+    return (isinstance(tr, torch.nn.Sequential) and len(tr) > 0 and all(isinstance(b, Block) for b in tr)
+            and all(hasattr(m, a) for a in ("input_proj", "cls_token", "pos_embed", "seq_len"))
+            and isinstance(head, torch.nn.Sequential) and len(head) == 3
+            and isinstance(head[0], torch.nn.LayerNorm) and isinstance(head[2], torch.nn.Linear))
+
 
 class _Plan:
     """What the skinny plan needs of a model: the module whose forward assembles the tokens, the encoder,
@@ -69,12 +105,19 @@ class _Plan:
     def __init__(self, model):
         self.why = None  # reason the model is outside the skinny contract
         self.spec = None
+        self.decompose = None  # ExpressionAwareViT: the model's own decomposer call
+        self.prenorm = False
         core = model
         if hasattr(model, "backbone") and hasattr(model, "_spec"):  # LatentViTv2
             core = model.backbone
             if model.use_spe or model.use_lwn or model.use_leam:
                 self.spec = model._spec
+        elif hasattr(model, "decomposer") and _is_hybrid(getattr(model, "vit", None)):  # ExpressionAwareViT
+            core = model.vit
         self.core = core
+        if _is_hybrid(core):
+            self._prenorm(model, core)
+            return
         enc = getattr(core, "transformer", None)
         if isinstance(enc, Encoder) and hasattr(core, "input_proj") and hasattr(core, "mlp_head"):
             self.kind = "latent"
@@ -89,7 +132,8 @@ class _Plan:
             self.head_ln, self.head_lin = core.norm, core.head
         else:
             self.kind = None
-            self.why = "the model is not a post-norm encoder stack (fervit.blocks.Encoder of EncoderLayers)"
+            self.why = ("the model is neither a post-norm encoder stack (fervit.blocks.Encoder of EncoderLayers) nor "
+                        "a HybridLatentViT / ExpressionAwareViT")
             return
         self.enc = enc
         lay = list(enc.layers)
@@ -101,13 +145,52 @@ class _Plan:
         if D % 8 or F % 8 or D > 1024:
             self.why = f"embed_dim {D} / mlp_dim {F} must be multiples of 8, embed_dim <= 1024"
 
+    def _prenorm(self, model, core):
+        """A HybridLatentViT `core`, on its own or as the `vit` of an ExpressionAwareViT `model`."""
+        self.kind, self.prenorm = "hybrid", True
+        self.N = core.seq_len + 1
+        self.blocks = list(core.transformer)
+        self.adapters = list(core.adapters) if getattr(core, "use_adapter", False) else None
+        self.head_ln, self.head_lin = core.head[0], core.head[2]
+        if model is core:
+            self.sample_shape = (core.seq_len, core.input_proj.in_features)
+        else:
+            dec = model.decomposer
+            self.sample_shape = (dec.seq_len, dec.latent_dim)
+            self.decompose = lambda x: dec(x, output_mode=model.output_mode, enhance_alpha=model.enhance_alpha,
+                                           decompose_mode=model.decompose_mode)
+            if model.use_spe or model.use_lwn or model.use_leam:
+                from modules._wplus import WplusSpec  # the package the model's class itself comes from
+
+                self.spec = lambda: WplusSpec(spe=getattr(model, "spe", None), lwn=getattr(model, "lwn", None),
+                                              leam=getattr(model, "leam", None))
+            tokens = dec.seq_len * (2 if model.output_mode == "concat" else 1)
+            if tokens != core.seq_len or dec.latent_dim != core.input_proj.in_features:
+                self.why = (f"the decomposer's output ({tokens} x {dec.latent_dim}) does not match the hybrid's input "
+                            f"({core.seq_len} x {core.input_proj.in_features})")
+                return
+        D = self.blocks[0].mlp.fc1.in_features
+        F = self.blocks[0].mlp.fc1.out_features
+        if D % 16 or F % 8 or D > 1024:
+            self.why = f"embed_dim {D} must be a multiple of 16 and <= 1024, mlp_dim {F} a multiple of 8"
+            return
+        if self.adapters is not None:
+            if len(self.adapters) != len(self.blocks) or not all(isinstance(a, AdapterModule) for a in self.adapters):
+                self.why = "the adapters are not one AdapterModule per block"
+                return
+            R = self.adapters[0].adapter[0].out_features
+            if R % 16 or not 16 <= R <= ADAPTER_MAX_WIDTH:
+                self.why = (f"the adapter width {R} is outside fer_skinny_adapter's contract (a multiple of 16, "
+                            f"16 <= width <= {ADAPTER_MAX_WIDTH})")
+
 
 class InferenceSession:
     def __init__(self, model: FerModule, batch_size: int = 1, skinny: str = "auto",
                  input_shape: Optional[Tuple[int, ...]] = None, warmup: int = 2):
         """model: a FerModule in eval() mode on a ROCm device; batch_size: the B every run() takes;
         skinny: "auto" / "on" / "off" (module doc); input_shape: per-sample input shape, needed only for
-        models the session cannot read it from (anything but LatentViT, LatentViTv2, ImageViT)."""
+        models the session cannot read it from (anything but LatentViT, LatentViTv2, ImageViT, HybridLatentViT,
+        ExpressionAwareViT)."""
         if skinny not in ("auto", "on", "off"):
             raise ValueError(f"InferenceSession: skinny must be 'auto', 'on' or 'off', not {skinny!r}")
         if not isinstance(model, FerModule):
@@ -134,7 +217,8 @@ class InferenceSession:
             why = f"batch_size * tokens = {rows} rows exceeds the skinny kernels' {SKINNY_MAX_ROWS}"
         if skinny == "on" and why is not None:
             raise RuntimeError(f"InferenceSession: skinny='on' but {why}")
-        self.skinny = why is None and (skinny == "on" or (skinny == "auto" and rows <= SKINNY_AUTO_MAX_ROWS))
+        auto_rows = SKINNY_AUTO_MAX_ROWS_PRENORM if plan.prenorm else SKINNY_AUTO_MAX_ROWS
+        self.skinny = why is None and (skinny == "on" or (skinny == "auto" and rows <= auto_rows))
         self.plan = plan
         shape = tuple(input_shape) if input_shape is not None else (plan.sample_shape if plan.kind else None)
         if shape is None:
@@ -166,7 +250,44 @@ class InferenceSession:
             return self.model(self.x_in).float()
         return self._skinny_forward()
 
+    def _prenorm_forward(self) -> torch.Tensor:
+        m, plan, B, N = self.model, self.plan, self.B, self.plan.N
+        core = plan.core
+        flat = m.fer_flat()
+        dt = torch.bfloat16
+        x = self.x_in
+        if plan.decompose is not None:
+            x = plan.decompose(x)
+        if plan.spec is not None:
+            x = plan.spec().run(x, flat, False)
+        cfg = LayerCfg(B=B, N=N, H=1, save=False)
+        t = LatentTokensFn.apply(x, cfg, flat, dt, core.input_proj.weight, core.input_proj.bias, core.cls_token,
+                                 core.pos_embed)
+        M, D = t.shape
+        for i, blk in enumerate(plan.blocks):
+            a, mlp = blk.attn, blk.mlp
+            H = a.num_heads
+            dh = D // H
+            ln1 = (blk.norm1.weight.data, blk.norm1.bias.data, blk.norm1.eps)
+            ln2 = (blk.norm2.weight.data, blk.norm2.bias.data, blk.norm2.eps)
+            qkv = ops.skinny_linear(t, flat.half_view(a.qkv.weight), a.qkv.bias.data, ln_a=ln1)
+            o = torch.empty(M, D, dtype=dt, device=t.device)
+            ops.attention_fwd(qkv, o, ops.attention_saved(qkv, B, N, H, dh), B, N, H, dh)
+            x1 = ops.skinny_linear(o, flat.half_view(a.proj.weight), a.proj.bias.data, res=t)
+            g = ops.skinny_linear(x1, flat.half_view(mlp.fc1.weight), mlp.fc1.bias.data, act="gelu", ln_a=ln2)
+            t = ops.skinny_linear(g, flat.half_view(mlp.fc2.weight), mlp.fc2.bias.data, res=x1)
+            if plan.adapters is not None:
+                fc1, fc2 = plan.adapters[i].adapter[0], plan.adapters[i].adapter[2]
+                t = ops.skinny_adapter(t, flat.half_view(fc1.weight), fc1.bias.data, flat.half_view(fc2.weight),
+                                       fc2.bias.data, plan.adapters[i].alpha.data)
+        # the head on the B CLS rows (row stride N): its LayerNorm is part of fer_head_fwd
+        ln, lin = plan.head_ln, plan.head_lin
+        logits, _ = ops.head_fwd(t, N, ln.weight.data, ln.bias.data, ln.eps, lin.weight.data, lin.bias.data, B)
+        return logits
+
     def _skinny_forward(self) -> torch.Tensor:
+        if self.plan.prenorm:
+            return self._prenorm_forward()
         m, plan, B, N = self.model, self.plan, self.B, self.plan.N
         core = plan.core
         flat = m.fer_flat()

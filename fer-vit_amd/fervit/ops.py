@@ -1145,3 +1145,30 @@ def skinny_linear(x, w, bias=None, *, act="none", ln_a=None, res=None, ln_res=No
                                   ptr(ba), ea, *_row(res, N), ptr(gr), ptr(br), er, out.data_ptr(), out.stride(0),
                                   M, N, K, stream()), "skinny_linear")
     return out
+
+
+def skinny_adapter(x, w1, b1, w2, b2, alpha, out=None):
+    """One fer_skinny_adapter launch for M <= 64 bf16 rows: out = x + alpha * (GELU(x w1^T + b1) w2^T + b2).
+    x / out [M, D], w1 [R, D], w2 [D, R] bf16 with unit column stride; b1 [R], b2 [D] contiguous fp32; alpha a
+    one-element fp32 device tensor, read by the kernel (never copied to the host). out must not overlap x. The
+    library checks the contract (M, D, R, strides, alignment, overlap) and the call raises FerError on a
+    violation."""
+    _dev(x)
+    M, D = x.shape
+    R = w1.shape[0]
+    for name, t in (("x", x), ("w1", w1), ("w2", w2), ("out", out)):
+        if t is not None and (t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1):
+            raise TypeError(f"skinny_adapter: {name} must be a bf16 [rows, cols] tensor with unit column stride")
+    for name, t in (("b1", b1), ("b2", b2), ("alpha", alpha)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError(f"skinny_adapter: {name} must be a contiguous fp32 device tensor")
+    if (tuple(w1.shape) != (R, D) or tuple(w2.shape) != (D, R) or b1.numel() != R or b2.numel() != D
+            or alpha.numel() != 1):
+        raise ValueError("skinny_adapter: x [M, D], w1 [R, D], b1 [R], w2 [D, R], b2 [D], alpha [1]")
+    out = _alloc(out, x, (M, D))
+    if tuple(out.shape) != (M, D):
+        raise ValueError("skinny_adapter: out must be [M, D]")
+    check(lib().fer_skinny_adapter(x.data_ptr(), x.stride(0), w1.data_ptr(), w1.stride(0), b1.data_ptr(),
+                                   w2.data_ptr(), w2.stride(0), b2.data_ptr(), alpha.data_ptr(), out.data_ptr(),
+                                   out.stride(0), M, D, R, stream()), "skinny_adapter")
+    return out

@@ -672,6 +672,23 @@ int fer_skinny_linear(const void* A, int64_t lda, const void* W, int64_t ldw, co
                       const float* gamma_r, const float* beta_r, float eps_r, void* out, int64_t ldc, int M, int N,
                       int K, fer_stream_t stream);
 
+/* The AdapterModule of the pre-norm models as one launch of the same plan (csrc/skinny_adapter.hip), bf16,
+ * M <= 64 rows:
+ *   out[M][D] = X + alpha * ( GELU_erf(X W1^T + b1) W2^T + b2 )
+ * X [M][ldx], W1 [R][ldw1], W2 [D][ldw2] (nn.Linear's layout) and out [M][ldc] are bf16; b1 [R], b2 [D] and
+ * alpha are fp32. alpha is a DEVICE pointer to one float (the module's parameter): the kernel reads it, the
+ * host never does, so the launch is sync-free and a captured launch follows later changes of the value.
+ * Accumulation is fp32; the hidden tile GELU(.) is rounded to bf16 once, as the second product's matrix
+ * operand; x + alpha * (. + b2) is formed in fp32 and rounded once on the store.
+ * Contract: 1 <= M <= 64; D % 16 == 0; R % 16 == 0 and 16 <= R <= 128; every ld covers its row and is a
+ * multiple of 8; every base pointer is 16-byte aligned (alpha: 4-byte); out must not overlap X (every
+ * workgroup reads the whole of X). Anything else returns a negative code and sets fer_last_error before any
+ * launch. D / 16 workgroups that never communicate, each recomputing the hidden tile (DESIGN.md section
+ * 2.13): the result is deterministic, and row m of the output does not depend on M or on the other rows. */
+int fer_skinny_adapter(const void* X, int64_t ldx, const void* W1, int64_t ldw1, const float* b1, const void* W2,
+                       int64_t ldw2, const float* b2, const float* alpha, void* out, int64_t ldc, int M, int D,
+                       int R, fer_stream_t stream);
+
 const char* fer_last_error(void);
 const char* fer_version(void);
 

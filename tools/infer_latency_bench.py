@@ -7,6 +7,8 @@ Models (the reference script's settings, bf16):
   latent_d2   LatentViT(depth=2, embed_dim=512, heads=8, seq_len=18)
   latent_d6   LatentViT at its default depth 6
   image_d2    ImageViT(img_size=224, patch_size=16, embed_dim=512, depth=2, heads=8, mlp_dim=2048)
+--family prenorm measures the pre-norm family instead (prenorm_models below: the tiny and the config-4 base
+HybridLatentViT with adapters at B = 1, 2, 3 and the tiny concat ExpressionAwareViT at B = 1), same arms.
 Arms, per model and batch size (the latent models at B = 1, 2, 3 and 8, the image model at B = 1):
   eager    model.eval() forward under torch.no_grad() -- the path before InferenceSession existed
   graph    InferenceSession(skinny="off"): the same forward replayed as a HIP graph
@@ -85,26 +87,62 @@ def time_arm(fn, warmup, iters):
     return [1e3 * a.elapsed_time(b) for a, b in ev]
 
 
+def prenorm_models():
+    """The pre-norm family (--family prenorm), 12 blocks each, w+ 18 x 512 inputs:
+      hybrid_tiny   HybridLatentViT, timm tiny geometry (D 192), adapters of width 64, B = 1, 2, 3
+      hybrid_base   BASELINE config 4: base geometry (D 768), adapters of width 64, B = 1, 2, 3
+      concat_tiny   ExpressionAwareViT(output_mode="concat") on the tiny hybrid: 37 token rows, B = 1
+    The adapters' alpha is set to 0.37 and their weights to N(0, 0.05^2) so that no launch works on zeros; the
+    decomposer's directions are seeded random unit vectors."""
+    from models_fer_vit.expression_aware_vit import ExpressionAwareViT
+    from models_fer_vit.hybrid_latent_vit import create_hybrid_latent_vit
+    from models_fer_vit.latent_decomposer import LatentDecomposer
+
+    def hybrid(size, seq_len=18):
+        m = create_hybrid_latent_vit(latent_dim=512, seq_len=seq_len, model_size=size, use_pretrained=False,
+                                     use_adapter=True, adapter_dim=64)
+        with torch.no_grad():
+            for n, p in m.named_parameters():
+                if n.endswith("alpha"):
+                    p.fill_(0.37)
+                elif n.startswith("adapters") and p.dim() == 2:
+                    p.normal_(0.0, 0.05)
+        return m
+
+    dec = LatentDecomposer({i: torch.randn(18, 512) for i in range(7)})
+    return {
+        "hybrid_tiny": (hybrid("tiny"), (18, 512), 19, (1, 2, 3)),
+        "hybrid_base": (hybrid("base"), (18, 512), 19, (1, 2, 3)),
+        "concat_tiny": (ExpressionAwareViT(dec, hybrid("tiny", 36), output_mode="concat"), (18, 512), 37, (1,)),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--family", choices=("postnorm", "prenorm"), default="postnorm",
+                    help="postnorm: the models above; prenorm: the HybridLatentViT / ExpressionAwareViT set")
     args = ap.parse_args()
 
     from fervit.infer import SKINNY_MAX_ROWS, InferenceSession
-    from models_fer_vit.image_vit import ImageViT
-    from models_fer_vit.latent_vit import LatentViT
 
     torch.manual_seed(0)
     dev = torch.device("cuda:0")
-    models = {
-        "latent_d2": (LatentViT(depth=2, embed_dim=512, heads=8, seq_len=18), (18, 512), 19, (1, 2, 3, 8)),
-        "latent_d6": (LatentViT(), (18, 512), 19, (1, 2, 3, 8)),
-        "image_d2": (ImageViT(img_size=224, patch_size=16, embed_dim=512, depth=2, heads=8, mlp_dim=2048),
-                     (3, 224, 224), 197, (1,)),
-    }
+    if args.family == "postnorm":
+        from models_fer_vit.image_vit import ImageViT
+        from models_fer_vit.latent_vit import LatentViT
+
+        models = {
+            "latent_d2": (LatentViT(depth=2, embed_dim=512, heads=8, seq_len=18), (18, 512), 19, (1, 2, 3, 8)),
+            "latent_d6": (LatentViT(), (18, 512), 19, (1, 2, 3, 8)),
+            "image_d2": (ImageViT(img_size=224, patch_size=16, embed_dim=512, depth=2, heads=8, mlp_dim=2048),
+                         (3, 224, 224), 197, (1,)),
+        }
+    else:
+        models = prenorm_models()
     arms = {}  # name -> (callable, launches)
     keep = []
     for name, (m, shape, tokens, batches) in models.items():
@@ -135,7 +173,8 @@ def main():
                       median=round(float(np.median(allv)), 2), p10=round(float(np.percentile(allv, 10)), 2),
                       p90=round(float(np.percentile(allv, 90)), 2), repeat_medians=[round(v, 2) for v in meds],
                       spread=round(max(meds) - min(meds), 2), launches=arms[k][1])
-    line = json.dumps(dict(tool="infer_latency_bench", unit="us", device=torch.cuda.get_device_name(0),
+    line = json.dumps(dict(tool="infer_latency_bench", family=args.family, unit="us",
+                           device=torch.cuda.get_device_name(0),
                            precision="bf16", warmup=args.warmup, iters=args.iters, repeats=args.repeats, arms=res))
     print(line)
     if args.out:
