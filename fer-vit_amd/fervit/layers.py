@@ -117,29 +117,23 @@ class _ReduceDefer:
         self.enabled = True
         self.mb = 64
         self.arena: Optional[torch.Tensor] = None
-        self.open = False
-        self.owner = -1  # autograd graph task whose end-of-backward callback closes the window
+        self._window = runtime.OncePerBackward(self._end)  # closes the window when its backward ends
         self.windows = 0  # backward passes that deferred (tests)
+
+    @property
+    def open(self) -> bool:
+        return self._window.queued
 
     def begin(self, device) -> bool:
         if not self.enabled or device is None or device.type != "cuda":
             return False
-        task = torch._C._current_graph_task_id()
-        if self.open and task != self.owner:
-            # the window's backward ended without running its callback (torch drops queued
-            # callbacks when a backward raises): run what it queued, then open a fresh window
-            self._end()
-        if not self.open:
+        if not self._window.current():  # (a window whose backward raised is closed here: its sums run)
             if self.arena is None or self.arena.device != device:
                 if torch.cuda.is_current_stream_capturing():
                     return False  # allocate in an eager step first (StepGraph warm-up)
                 self.arena = torch.empty(self.mb << 18, dtype=torch.float32, device=device)
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(self._end)
-            except RuntimeError:  # not inside a backward pass
+            if not self._window.arm():  # not inside a backward pass
                 return False
-            self.open = True
-            self.owner = task
             self.windows += 1
         check(lib().fer_reduce_defer(1, self.arena.data_ptr(), self.arena.numel() * 4, ops.stream()), "reduce_defer")
         return True
@@ -152,15 +146,13 @@ class _ReduceDefer:
             check(lib().fer_reduce_flush(), "reduce_flush")
 
     def _end(self) -> None:
-        self.open = False
-        self.owner = -1
         check(lib().fer_reduce_defer(0, None, 0, None), "reduce_defer")
 
     def close_if_open(self) -> None:
         """Readers of the gradients (optimizer step, clipping) outside a backward: a window still
         open here lost its callback to an exception in its backward -- run its queued sums now."""
-        if self.open and torch._C._current_graph_task_id() == -1:
-            self._end()
+        if torch._C._current_graph_task_id() == -1:
+            self._window.current()
 
 
 REDUCE = _ReduceDefer()

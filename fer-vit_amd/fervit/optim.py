@@ -7,12 +7,39 @@ and the bf16 compute copy refreshed in the same pass.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from typing import Optional
 
 import torch
 
 from . import ops, runtime
 from ._lib import AdamWSegment, check, lib
+
+
+@dataclasses.dataclass
+class SegTable:
+    """A device AdamW segment table and what launching it takes."""
+    dev: torch.Tensor  # AdamWSegment[nseg]
+    nseg: int
+    maxn: int          # numel of the largest segment
+    pairs: list        # (param group index, parameter) of every segment
+    sig: tuple         # (offset, numel, lr, weight_decay, beta1, beta2, eps) of every segment
+    steps: tuple       # host step of every segment at the table's last launch
+    # device step count the kernel adds to every segment's step: the table's own (a resident table,
+    # advanced by one launch per reuse), the StepGraph's (the frozen table), or none
+    counter: Optional[torch.Tensor] = None
+    # transposed-copy segments and tile count of the table's own 2-D parameters (FlatParams.
+    # half_t_segments); None: the caller refreshes the whole store (mark_half_fresh)
+    tsegs: Optional[torch.Tensor] = None
+    tiles: int = 0
+    hp: Optional[list] = None  # the frozen table: the param groups' hyper-parameters it was written with
+
+    def advances(self, sig, steps) -> bool:
+        """A resident table serves a launch again only if it has the same segments and hyper-parameters
+        and every parameter's host step moved by exactly one since its last launch (its device step =
+        table step + counter advances by one per reuse); anything else -- another update path, a
+        different subset, graph replays, a scheduler's step -- rebuilds it."""
+        return sig == self.sig and all(s == t + 1 for s, t in zip(steps, self.steps))
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -23,22 +50,19 @@ class FusedAdamW(torch.optim.Optimizer):
         self.model = model
         self._flat = None
         self._m = self._v = None
-        self._segs_dev = None
-        self._seg_key = None
         self.grad_scale = 1.0        # e.g. 1/world after an all-reduce sum
         self.clip_coef: Optional[torch.Tensor] = None  # device scalar, consumed by the next step
-        self._step_counter: Optional[torch.Tensor] = None  # graph mode (freeze_for_graph)
-        self._frozen = None
+        self._frozen: Optional[SegTable] = None  # graph mode (freeze_for_graph)
         # eager mode: the segment table stays on the device between steps and the per-step bias-
         # correction step comes from a device counter (step = table step + *counter, advanced by one
         # stream-ordered launch per step) -- no per-step pinned allocation and H2D copy. Re-uploaded
         # when the segment set or any hyper-parameter changes.
         self.cache_table = True
-        self._eager = None  # (device table, nseg, maxn, signature, counter, host steps of its last launch)
+        self._eager: Optional[SegTable] = None
         # step_in_backward(): per-layer updates issued from the backward's gradient-ready hook
         self._inbw = False
         self._bw_done = set()     # ids of parameters already updated in the current backward
-        self._bw_tables = {}      # parameter-set key -> (device table, nseg, maxn, signature, counter, tsegs, tiles)
+        self._bw_tables = {}      # ids of a layer's parameters -> its resident SegTable
         self._pgroup = None       # id(p) -> param group index
 
     def zero_grad(self, set_to_none: bool = True):
@@ -58,8 +82,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._flat = flat
             self._m = torch.zeros_like(flat.data)
             self._v = torch.zeros_like(flat.data)
-            self._eager = None  # the resident segment tables hold the old store's offsets
-            self._bw_tables = {}
+            self._drop_tables()  # they hold the old store's offsets
             if old is not None:
                 # the store was rebuilt (a real .to() / .double().float(), a re-run after a child ran
                 # alone): parameters that are still the same objects keep their moments. `old.params`
@@ -104,8 +127,7 @@ class FusedAdamW(torch.optim.Optimizer):
         return sd
 
     def load_state_dict(self, state_dict):
-        self._eager = None
-        self._bw_tables = {}
+        self._drop_tables()
         super().load_state_dict(state_dict)
         flat = self._bind()
         with torch.no_grad():
@@ -128,15 +150,10 @@ class FusedAdamW(torch.optim.Optimizer):
         change of a group's lr / weight_decay / betas / eps (an LR scheduler's step) is written
         into the same device table before the next replay (sync_graph_hparams)."""
         flat = self._bind()
-        self._eager = None
-        self._bw_tables = {}
-        segs, maxn = self._segments(flat, bump=False)
-        self._frozen = (self._upload(segs, flat), len(segs), maxn)
-        # group of every segment (same walk as _segments), to rebuild the table with new hparams
-        self._frozen_groups = [gi for gi, g in enumerate(self.param_groups) for p in g["params"] if p.grad is not None]
-        self._frozen_segs = segs
-        self._frozen_hp = self._hparams()
-        self._step_counter = counter
+        self._drop_tables()
+        pairs = self._pairs()
+        self._frozen = self._table(flat, pairs, *self._scan(flat, pairs, bump=False), counter=counter)
+        self._frozen.hp = self._hparams()
 
     # ---- optimizer step inside the backward (opt-in)
     def step_in_backward(self, on: bool = True) -> "FusedAdamW":
@@ -173,48 +190,20 @@ class FusedAdamW(torch.optim.Optimizer):
         ps = [p for p in params if id(p) in self._pgroup and p.grad is not None]
         if not ps:
             return
-        segs, maxn = [], 0
-        for p in ps:
-            if p.grad.data_ptr() != flat.grad_views[id(p)].data_ptr():
-                return  # a foreign .grad tensor: leave this layer to step()
-        for p in ps:
-            g = self.param_groups[self._pgroup[id(p)]]
-            st = self.state[p]
-            st["step"] = st.get("step", 0) + 1
-            b1, b2 = g["betas"]
-            segs.append((flat.offsets[id(p)], p.numel(), g["lr"], g["weight_decay"], b1, b2, g["eps"], st["step"]))
-            maxn = max(maxn, p.numel())
+        if any(p.grad.data_ptr() != flat.grad_views[id(p)].data_ptr() for p in ps):
+            return  # a foreign .grad tensor: leave this layer to step()
+        pairs = [(self._pgroup[id(p)], p) for p in ps]
+        maxn, sig, steps = self._scan(flat, pairs, bump=True)
         key = tuple(id(p) for p in ps)
-        sig = tuple(x[:7] for x in segs)
-        steps = tuple(x[7] for x in segs)
-        e = self._bw_tables.get(key)
-        # reuse the resident table only if every parameter's host step moved by exactly one since the
-        # table's last launch (its device step = table step + counter advances by one per reuse);
-        # anything else -- another update path, a different subset, graph replays -- rebuilds it
-        advance = e is not None and e[3] == sig and all(s == t + 1 for s, t in zip(steps, e[7]))
-        if not advance:
-            dev = self._upload(segs, flat)
-            counter = torch.zeros(1, dtype=torch.int64, device=flat.data.device)
-            tsegs, tiles = flat.half_t_segments(ps)
-            e = (dev, len(segs), maxn, sig, counter, tsegs, tiles, steps)
-        dev, nseg, maxn, _, counter, tsegs, tiles, _ = e
-        if tsegs is None and flat.half_t is not None:  # the transposed copies appeared after the table was built
-            tsegs, tiles = flat.half_t_segments(ps)
-        self._bw_tables[key] = (dev, nseg, maxn, sig, counter, tsegs, tiles, steps)
+        t = self._bw_tables.get(key)
+        advance = t is not None and t.advances(sig, steps)
+        if advance:
+            t.steps = steps
+        else:
+            t = self._bw_tables[key] = self._table(flat, pairs, maxn, sig, steps, counter=True, own_t=True)
         self._eager = None  # these parameters' steps moved outside step()'s resident table
-        half = flat.bf16()
-
-        def launch():
-            if advance:
-                check(lib().fer_step_advance(counter.data_ptr(), ops.stream()), "adamw step")
-            check(lib().fer_adamw(flat.data.data_ptr(), flat.grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                                  half.data_ptr(), dev.data_ptr(), nseg, maxn, float(self.grad_scale), None,
-                                  counter.data_ptr(), ops.stream()), "adamw")
-            if tsegs is not None and flat.half_t is not None:
-                check(lib().fer_transpose_bf16_segments(half.data_ptr(), flat.half_t.data_ptr(), tsegs.data_ptr(),
-                                                        tsegs.shape[0], tiles, ops.stream()), "transpose")
-
-        runtime.WGRAD.run(launch, flat.grad)
+        flat.bf16()  # (a stale shadow is cast on the compute stream, not beside the backward)
+        runtime.WGRAD.run(lambda: self._launch(flat, t, advance), flat.grad)
         self._bw_done.update(key)
 
     def _hparams(self):
@@ -225,65 +214,87 @@ class FusedAdamW(torch.optim.Optimizer):
         CosineAnnealingLR.step() at an epoch end, `train/train_latent_vit_v2.py:368-370`), rewrite
         the captured segment table in place (a stream-ordered copy ahead of the replay: the
         replayed AdamW node reads it from device memory). Returns True when it rewrote it."""
-        if self._frozen is None:
+        t = self._frozen
+        if t is None:
             return False
         hp = self._hparams()
-        if hp == self._frozen_hp:
+        if hp == t.hp:
             return False
-        if len(hp) != len(self._frozen_hp):
+        if len(hp) != len(t.hp):
             raise RuntimeError("FusedAdamW: param groups changed under a captured StepGraph; release() it first")
-        segs = []
-        for gi, (off, n, _lr, _wd, _b1, _b2, _eps, step) in zip(self._frozen_groups, self._frozen_segs):
-            g = self.param_groups[gi]
-            b1, b2 = g["betas"]
-            segs.append((off, n, g["lr"], g["weight_decay"], b1, b2, g["eps"], step))
-        self._frozen[0].copy_(self._upload(segs, self._flat), non_blocking=True)
-        self._frozen_segs = segs
-        self._frozen_hp = hp
+        _, t.sig, _ = self._scan(self._flat, t.pairs, bump=False)  # (the steps stay those of the capture)
+        t.dev.copy_(self._upload(t.sig, t.steps, self._flat), non_blocking=True)
+        t.hp = hp
         return True
 
     def unfreeze(self) -> None:
         """Leave graph mode (StepGraph.release): the replays' device step count is folded into
         every parameter's host 'step', so state_dict() and later eager steps continue the bias
         correction where the replays left it."""
-        if self._step_counter is not None:
-            n = int(self._step_counter.item())
-            if n:
-                for g in self.param_groups:
-                    for p in g["params"]:
-                        st = self.state.get(p)
-                        if st is not None and "step" in st:
-                            st["step"] = st["step"] + n
-        self._frozen = None
-        self._step_counter = None
+        t, self._frozen = self._frozen, None
+        n = int(t.counter.item()) if t is not None else 0
+        if n:
+            for g in self.param_groups:
+                for p in g["params"]:
+                    st = self.state.get(p)
+                    if st is not None and "step" in st:
+                        st["step"] = st["step"] + n
+        self._drop_tables()
+
+    def _drop_tables(self) -> None:
+        """The resident tables no longer describe the store or the steps: the next launch rebuilds."""
         self._eager = None
         self._bw_tables = {}
 
-    def _segments(self, flat, bump: bool):
-        segs = []
-        maxn = 0
-        for g in self.param_groups:
-            b1, b2 = g["betas"]
-            for p in g["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if bump:
-                    st["step"] = st.get("step", 0) + 1
-                n = p.numel()
-                maxn = max(maxn, n)
-                segs.append((flat.offsets[id(p)], n, g["lr"], g["weight_decay"], b1, b2, g["eps"],
-                             st.get("step", 0)))
-                if p.grad.data_ptr() != flat.grad_views[id(p)].data_ptr():
-                    flat.grad_views[id(p)].copy_(p.grad)
-        return segs, maxn
+    def _pairs(self):
+        return [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"] if p.grad is not None]
+
+    def _walk(self, flat, pairs, bump: bool):
+        """(numel, signature, host step) of the segment of every (param group index, parameter) pair;
+        `bump` counts one more step first. A foreign `.grad` tensor is copied into the flat buffer."""
+        for gi, p in pairs:
+            g = self.param_groups[gi]
+            st = self.state[p]
+            if bump:
+                st["step"] = st.get("step", 0) + 1
+            gv = flat.grad_views[id(p)]
+            if p.grad is not None and p.grad.data_ptr() != gv.data_ptr():
+                gv.copy_(p.grad)
+            n = p.numel()
+            yield n, (flat.offsets[id(p)], n, g["lr"], g["weight_decay"], *g["betas"], g["eps"]), st.get("step", 0)
+
+    def _scan(self, flat, pairs, bump: bool):
+        """(largest numel, signature, host steps) of a non-empty list of pairs (see _walk)."""
+        ns, sig, steps = zip(*self._walk(flat, pairs, bump))
+        return max(ns), sig, steps
+
+    def _table(self, flat, pairs, maxn, sig, steps, counter=None, own_t: bool = False) -> SegTable:
+        """Upload a table. counter=True: a counter of its own, starting at zero; own_t: the table's launch
+        refreshes the transposed copies of its own parameters."""
+        t = SegTable(self._upload(sig, steps, flat), len(sig), maxn, pairs, sig, steps, counter)
+        if counter is True:
+            t.counter = torch.zeros(1, dtype=torch.int64, device=flat.data.device)
+        if own_t:
+            t.tsegs, t.tiles = flat.half_t_segments([p for _, p in pairs])
+        return t
+
+    def _launch(self, flat, t: SegTable, advance: bool, clip: Optional[torch.Tensor] = None) -> None:
+        """One update of the table's segments on the current stream: its counter advanced (a reused
+        resident table), the fused AdamW launch, the transposed copies of its own parameters."""
+        if advance:
+            check(lib().fer_step_advance(t.counter.data_ptr(), ops.stream()), "adamw step")
+        half = flat.bf16()
+        check(lib().fer_adamw(flat.data.data_ptr(), flat.grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                              half.data_ptr(), t.dev.data_ptr(), t.nseg, t.maxn, float(self.grad_scale),
+                              ops.ptr(clip), ops.ptr(t.counter), ops.stream()), "adamw")
+        flat.transpose_segments(t.tsegs, t.tiles)
 
     @staticmethod
-    def _upload(segs, flat):
+    def _upload(sig, steps, flat):
         """Segment table -> device through pinned memory, stream-ordered: a pageable blocking
         copy would make the host wait for the whole step's kernels every optimizer step, and
         the GPU then idle while the next step's first launches are issued."""
-        arr = (AdamWSegment * len(segs))(*[AdamWSegment(*s) for s in segs])
+        arr = (AdamWSegment * len(sig))(*[AdamWSegment(*s, t) for s, t in zip(sig, steps)])
         host = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr))),
                                 dtype=torch.uint8)
         if flat.data.is_cuda:
@@ -302,73 +313,30 @@ class FusedAdamW(torch.optim.Optimizer):
             if self._take_clip() is not None:
                 raise RuntimeError("FusedAdamW.step_in_backward: gradient clipping between backward and step() "
                                    "cannot apply to updates already made; disable step_in_backward")
-            rest = [p for g in self.param_groups for p in g["params"] if p.grad is not None and id(p) not in done]
-            if rest:
-                self._step_subset(flat, rest)
-            flat.mark_half_fresh(refresh=False)  # (each layer's transposed copies were refreshed with it)
+            rest = [(gi, p) for gi, p in self._pairs() if id(p) not in done]
+            if rest:  # the parameters the hook did not reach: one eager update of those only
+                self._launch(flat, self._table(flat, rest, *self._scan(flat, rest, bump=True), own_t=True), False)
+            flat.mark_half_fresh(refresh=False)  # (each table's transposed copies were refreshed with it)
             return loss
         if self._frozen is not None:  # graph mode: static segments, device step counter
-            dev, nseg, maxn = self._frozen
-            half = flat.bf16()
-            check(lib().fer_adamw(flat.data.data_ptr(), flat.grad.data_ptr(), self._m.data_ptr(),
-                                  self._v.data_ptr(), half.data_ptr(), dev.data_ptr(), nseg, maxn,
-                                  float(self.grad_scale), ops.ptr(self._take_clip()),
-                                  self._step_counter.data_ptr(), ops.stream()), "adamw")
+            self._launch(flat, self._frozen, False, self._take_clip())
             flat.mark_half_fresh()
             return loss
-        segs, maxn = self._segments(flat, bump=True)
-        if not segs:
+        pairs = self._pairs()
+        if not pairs:
             return loss
-        counter = None
-        sig = tuple(s[:7] for s in segs)
-        steps = tuple(s[7] for s in segs)
-        e = self._eager
-        if (self.cache_table and e is not None and e[3] == sig and flat.data.is_cuda
-                and all(s == t + 1 for s, t in zip(steps, e[5]))):
-            # same segments and hyper-parameters as the resident table, every step bumped by one since
-            dev, counter = e[0], e[4]
-            check(lib().fer_step_advance(counter.data_ptr(), ops.stream()), "adamw step")
-            self._eager = e[:5] + (steps,)
-        else:
-            dev = self._upload(segs, flat)
-            self._eager = None
-            if self.cache_table and flat.data.is_cuda:
-                counter = torch.zeros(1, dtype=torch.int64, device=flat.data.device)
-                self._eager = (dev, len(segs), maxn, sig, counter, steps)
-        self._segs_dev = dev
-        half = flat.bf16()
-        check(lib().fer_adamw(flat.data.data_ptr(), flat.grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                              half.data_ptr(), dev.data_ptr(), len(segs), maxn, float(self.grad_scale),
-                              ops.ptr(self._take_clip()), ops.ptr(counter), ops.stream()), "adamw")
+        maxn, sig, steps = self._scan(flat, pairs, bump=True)
+        resident = self.cache_table and flat.data.is_cuda
+        t = self._eager
+        advance = resident and t is not None and t.advances(sig, steps)
+        if advance:
+            t.steps = steps
+        else:  # (without cache_table: uploaded every step, no device counter)
+            t = self._table(flat, pairs, maxn, sig, steps, counter=True if resident else None)
+            self._eager = t if resident else None
+        self._launch(flat, t, advance, self._take_clip())
         flat.mark_half_fresh()
         return loss
-
-    def _step_subset(self, flat, params) -> None:
-        """One eager update of `params` only (the ones step_in_backward's hook did not reach)."""
-        self._eager = None  # steps move outside the resident table (the per-layer tables check theirs)
-        ids = {id(p) for p in params}
-        segs, maxn = [], 0
-        for g in self.param_groups:
-            b1, b2 = g["betas"]
-            for p in g["params"]:
-                if id(p) not in ids:
-                    continue
-                st = self.state[p]
-                st["step"] = st.get("step", 0) + 1
-                segs.append((flat.offsets[id(p)], p.numel(), g["lr"], g["weight_decay"], b1, b2, g["eps"], st["step"]))
-                maxn = max(maxn, p.numel())
-                if p.grad.data_ptr() != flat.grad_views[id(p)].data_ptr():
-                    flat.grad_views[id(p)].copy_(p.grad)
-        dev = self._upload(segs, flat)
-        self._segs_dev = dev
-        half = flat.bf16()
-        check(lib().fer_adamw(flat.data.data_ptr(), flat.grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                              half.data_ptr(), dev.data_ptr(), len(segs), maxn, float(self.grad_scale), None, None,
-                              ops.stream()), "adamw")
-        tsegs, tiles = flat.half_t_segments(params)
-        if tsegs is not None and flat.half_t is not None:
-            check(lib().fer_transpose_bf16_segments(half.data_ptr(), flat.half_t.data_ptr(), tsegs.data_ptr(),
-                                                    tsegs.shape[0], tiles, ops.stream()), "transpose")
 
     def _take_clip(self) -> Optional[torch.Tensor]:
         """The pending clip coefficient (set by clip_grad_norm_ through `optimizer=` or left on

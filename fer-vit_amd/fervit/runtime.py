@@ -172,9 +172,7 @@ class FlatParams:
 
     def half_t_segments(self, params):
         """(device segment table, tile count) of the transposed-copy refresh for the 2-D parameters in
-        `params` (None when there are none or no transposed copy exists yet)."""
-        if self.half_t is None:
-            return None, 0
+        `params`; (None, 0) when none of them is 2-D."""
         segs, tiles = [], 0
         for q in params:
             if q.dim() == 2:
@@ -189,27 +187,25 @@ class FlatParams:
         return self.view(p, self.bf16())
 
     # ---- transposed bf16 copies (dgrad operands, K-contiguous)
-    def refresh_half_t(self):
-        if self.half_t is None or self.half is None:
+    def transpose_segments(self, tsegs, tiles) -> None:
+        """One batched transpose launch: the transposed copies of the segments in `tsegs` (a table from
+        half_t_segments) follow the bf16 shadow. Nothing to do before both buffers exist."""
+        if tsegs is None or self.half_t is None or self.half is None:
             return
         from ._lib import check, lib
         from . import ops
 
-        check(lib().fer_transpose_bf16_segments(self.half.data_ptr(), self.half_t.data_ptr(), self._tsegs.data_ptr(),
-                                                self._tsegs.shape[0], self._ttiles, ops.stream()), "transpose")
+        check(lib().fer_transpose_bf16_segments(self.half.data_ptr(), self.half_t.data_ptr(), tsegs.data_ptr(),
+                                                tsegs.shape[0], tiles, ops.stream()), "transpose")
+
+    def refresh_half_t(self):
+        self.transpose_segments(self._tsegs, self._ttiles)
 
     def half_t_view(self, p):
         """bf16 W^T ([cols][rows]) of a 2-D parameter, kept in step with the bf16 shadow: one
         batched transpose launch per refresh of the shadow (optimizer step or cast)."""
         if self.half_t is None:
-            segs, tiles = [], 0
-            for q in self.params:
-                if q.dim() == 2:
-                    r, c = q.shape
-                    segs.append((self.offsets[id(q)], r, c, tiles))
-                    tiles += -(-r // 64) * -(-c // 64)
-            self._tsegs = torch.tensor(segs, dtype=torch.int64).to(self.device)
-            self._ttiles = tiles
+            self._tsegs, self._ttiles = self.half_t_segments(self.params)
             self.bf16()
             self.half_t = torch.empty(self.numel, dtype=torch.bfloat16, device=self.device)
             self.refresh_half_t()
@@ -277,6 +273,42 @@ def grads_ready(params) -> None:
         h(params)
 
 
+class OncePerBackward:
+    """Queues `fn` on the autograd engine at most once per backward pass (graph task): `fn` runs when
+    that backward ends. Torch drops queued callbacks when a backward raises; the task id kept here
+    shows that at the next use, in another backward or outside one: the stale callback is run first
+    (its window is finished), then `fn` is queued for the new backward."""
+
+    def __init__(self, fn):
+        self.fn = fn
+        self.task = -1  # graph task whose end runs fn; -1: not queued
+
+    @property
+    def queued(self) -> bool:
+        return self.task != -1
+
+    def current(self) -> bool:
+        """Queued for the backward pass that is running now (a stale one is finished first)."""
+        if self.task != -1 and self.task != torch._C._current_graph_task_id():
+            self.fire()
+        return self.task != -1
+
+    def arm(self) -> bool:
+        """Queue fn unless this backward has it already. False: not inside a backward pass, nothing
+        is queued and the caller does now what fn would have done."""
+        if not self.current():
+            try:
+                torch.autograd.Variable._execution_engine.queue_callback(self.fire)
+            except RuntimeError:
+                return False
+            self.task = torch._C._current_graph_task_id()
+        return True
+
+    def fire(self) -> None:
+        self.task = -1
+        self.fn()
+
+
 # ------------------------------------------------------------ weight-gradient stream
 class _WgradStream:
     """Weight gradients (dW = dY^T X) on a second HIP stream.
@@ -298,7 +330,7 @@ class _WgradStream:
 
     def __init__(self):
         self.streams = {}
-        self.join_queued = False
+        self._join = OncePerBackward(self.sync)
         self.enabled = True
         self.in_capture = False
         # CU mask of the side stream (list of 32-bit words, bit i = CU i; None: every CU). Set before
@@ -307,22 +339,36 @@ class _WgradStream:
         # legacy null stream it serialises with it, so run the step on a non-blocking stream when a mask
         # is set (tools/step_ab.py does).
         self.cu_mask: Optional[List[int]] = None
-        self._handles = {}
-        self._retired = []  # masked handles of earlier reset()s, never destroyed (see reset)
+        self._masked = {}  # (device, mask words) -> stream, for the life of the process (see reset)
 
-    def _make(self, dev):
-        if not self.cu_mask:
-            return torch.cuda.Stream(device=dev)
+    @property
+    def join_queued(self) -> bool:
+        return self._join.queued
+
+    @staticmethod
+    def _create_masked(dev, words):
         import ctypes
 
         from ._lib import check, lib
 
-        words = (ctypes.c_uint32 * len(self.cu_mask))(*[int(w) & 0xFFFFFFFF for w in self.cu_mask])
         h = ctypes.c_void_p()
         with torch.cuda.device(dev):
-            check(lib().fer_stream_create_cu_mask(words, len(self.cu_mask), 0, ctypes.byref(h)), "wgrad stream")
-        self._handles[dev] = h.value
+            check(lib().fer_stream_create_cu_mask((ctypes.c_uint32 * len(words))(*words), len(words), 0,
+                                                  ctypes.byref(h)), "wgrad stream")
         return torch.cuda.ExternalStream(h.value, device=dev)
+
+    def _side(self, dev):
+        side = self.streams.get(dev)
+        if side is None:
+            if self.cu_mask:
+                key = (dev, tuple(int(w) & 0xFFFFFFFF for w in self.cu_mask))
+                if key not in self._masked:
+                    self._masked[key] = self._create_masked(*key)
+                side = self._masked[key]
+            else:
+                side = torch.cuda.Stream(device=dev)
+            self.streams[dev] = side
+        return side
 
     def reset(self):
         """Drop the side streams (e.g. after changing cu_mask); call with no backward in flight.
@@ -330,12 +376,11 @@ class _WgradStream:
         A CU-masked stream's handle is NOT destroyed: tensors such as flat.grad carry it from
         record_stream(), and the caching allocator records an event on it whenever such a tensor is
         freed, however much later -- on a destroyed handle that is an invalid-handle error or a
-        silently reused one. The handles stay alive for the life of the process (_retired)."""
+        silently reused one. Each (device, mask) keeps its one stream for the life of the process, and
+        the next use under the same mask gets it back."""
         if self.streams:
             torch.cuda.synchronize()
         self.streams = {}
-        self._retired.extend(self._handles.values())
-        self._handles = {}
 
     def _off(self) -> bool:
         return not self.enabled or (not self.in_capture and torch.cuda.is_current_stream_capturing())
@@ -348,25 +393,15 @@ class _WgradStream:
         if self._off():
             return fn()
         main = torch.cuda.current_stream(dev)
-        side = self.streams.get(dev)
-        if side is None:
-            side = self.streams[dev] = self._make(dev)
+        side = self._side(dev)
         side.wait_stream(main)
         with torch.cuda.stream(side):
             out = fn()
         for t in inputs:
             t.record_stream(side)
-        if not self.join_queued:
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(self._join)
-                self.join_queued = True
-            except RuntimeError:  # not inside a backward pass: join right away
-                self._join()
+        if not self._join.arm():  # not inside a backward pass: join right away
+            self.sync()
         return out
-
-    def _join(self):
-        self.join_queued = False
-        self.sync()
 
     def sync(self):
         """The current (compute) stream waits for every weight gradient issued so far."""

@@ -401,13 +401,120 @@ def test_step_in_backward_second_backward_raises():
         with pytest.raises(RuntimeError, match="second backward"):
             crit(m(x), y).backward()
     finally:
-        from fervit import runtime
-        from fervit.optim import _close_reduce_window
-
         opt.step_in_backward(False)
-        # the raising backward dropped its queued engine callbacks: join the weight-gradient stream and
-        # close the deferred-reduction window by hand so later tests start clean
-        runtime.WGRAD.join_queued = False
-        runtime.WGRAD.sync()
-        _close_reduce_window()
         torch.cuda.synchronize()
+
+
+def _small_image_vit():
+    from models_fer_vit.image_vit import ImageViT
+
+    torch.manual_seed(0)
+    m = ImageViT(img_size=48, patch_size=16, embed_dim=64, depth=1, heads=2, mlp_dim=128, dropout=0.0)
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn(4, 3, 48, 48, generator=g).to(DEV)
+    y = torch.randint(0, 7, (4,), generator=g).to(DEV)
+    return m.to(DEV).set_precision("bf16"), x, y
+
+
+def test_step_in_backward_subset_update_equals_step():
+    """The parameters step_in_backward's hook does not reach are updated by step() alone, from a table of
+    their own: the head weight takes no gradient from the backward (requires_grad=False) and gets a hand-made
+    foreign `.grad` after it. Two such steps == the same two under plain step(), bit for bit: parameters,
+    both moments, the bf16 shadow, the transposed copies of the 2-D parameters, every host step count."""
+    from fervit.loss import CrossEntropyLoss
+    from fervit.optim import FusedAdamW
+
+    crit = CrossEntropyLoss(label_smoothing=0.1)
+    g = torch.Generator().manual_seed(9)
+    hand = [torch.randn(7, 64, generator=g).to(DEV) for _ in range(2)]
+    out = []
+    for inbw in (False, True):
+        m, x, y = _small_image_vit()
+        m.head.weight.requires_grad_(False)
+        opt = FusedAdamW(m.parameters(), lr=1e-3, weight_decay=0.05, model=m).step_in_backward(inbw)
+        for h in hand:
+            opt.zero_grad()
+            crit(m(x), y).backward()
+            assert m.head.weight.grad is None
+            m.head.weight.grad = h.clone()
+            opt.step()
+        opt.step_in_backward(False)
+        torch.cuda.synchronize()
+        flat = m.fer_flat()
+        assert flat.half is not None and flat.half_t is not None
+        out.append((flat.data.clone(), opt._m.clone(), opt._v.clone(), flat.half.view(torch.int16).clone(),
+                    [flat.half_t_view(p).view(torch.int16).clone() for p in m.parameters() if p.dim() == 2],
+                    [opt.state[p]["step"] for p in m.parameters()]))
+    a, b = out
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
+    assert torch.equal(a[3], b[3])
+    assert len(a[4]) == len(b[4]) > 0 and all(torch.equal(u, v) for u, v in zip(a[4], b[4]))
+    assert a[5] == b[5] == [2] * len(a[5])
+
+
+@pytest.mark.parametrize("how", ["second_backward", "hook_raises"])
+def test_backward_windows_heal_after_a_backward_that_raised(how):
+    """A backward that raises drops the engine callbacks that join the weight-gradient stream and close the
+    deferred-reduction window. With no cleanup by hand, the next ordinary backward finishes the stale windows
+    and gets its own: when it returns both are closed, and its gradients equal, bit for bit, those of the
+    same backward before the process saw the error. The raise is step_in_backward's refusal of a second
+    backward (from the head's hook call, before any weight gradient of that pass), or an error from the last
+    gradient-ready hook call of the pass (after all of them)."""
+    from fervit import runtime
+    from fervit.layers import REDUCE
+    from fervit.loss import CrossEntropyLoss
+    from fervit.optim import FusedAdamW
+
+    crit = CrossEntropyLoss()
+    m, x, y = _small_image_vit()
+    sd = {k: v.clone() for k, v in m.state_dict().items()}
+    calls = []
+
+    def count(params):
+        calls.append(1)
+
+    def ordinary_backward():
+        opt = FusedAdamW(m.parameters(), lr=1e-3, model=m)
+        opt.zero_grad()
+        crit(m(x), y).backward()
+        state = (runtime.WGRAD.join_queued, REDUCE.open)  # directly after backward() returns
+        return state, {n: p.grad.clone() for n, p in m.named_parameters()}
+
+    runtime.register_grad_ready_hook(count)
+    try:
+        _, ref = ordinary_backward()
+    finally:
+        runtime.remove_grad_ready_hook(count)
+    if how == "second_backward":
+        opt = FusedAdamW(m.parameters(), lr=1e-3, model=m).step_in_backward(True)
+        try:
+            opt.zero_grad()
+            crit(m(x), y).backward()
+            with pytest.raises(RuntimeError, match="second backward"):
+                crit(m(x), y).backward()
+        finally:
+            opt.step_in_backward(False)
+        assert REDUCE.open
+        m.load_state_dict(sd)  # (the first backward's hook updated the parameters)
+    else:
+        left = [len(calls)]
+
+        def boom(params):
+            left[0] -= 1
+            if left[0] == 0:
+                raise RuntimeError("injected backward failure")
+
+        runtime.register_grad_ready_hook(boom)
+        try:
+            m.zero_grad(set_to_none=True)
+            with pytest.raises(RuntimeError, match="injected"):
+                crit(m(x), y).backward()
+        finally:
+            runtime.remove_grad_ready_hook(boom)
+        assert runtime.WGRAD.join_queued and REDUCE.open
+    state, got = ordinary_backward()
+    assert state == (False, False)
+    assert got.keys() == ref.keys()
+    for k in ref:
+        assert torch.equal(got[k], ref[k]), k
+    torch.cuda.synchronize()
