@@ -1,8 +1,8 @@
 """The harness the element-wise kernel tests share (tests/test_gpu_convbn.py, test_gpu_attnpool.py,
 test_gpu_rowops.py, test_gpu_gemm_elementwise.py, test_gpu_grouped_gemm.py, test_gpu_highway.py,
-test_gpu_attention_elementwise.py, test_gpu_edge_kernels.py, test_gpu_optim_kernels.py): access to the
-C ABI, and operands as views into NaN-filled parents whose guard rows and padding columns must keep their
-bits. The bound arithmetic is tests/elemwise.py.
+test_gpu_attention_elementwise.py, test_gpu_edge_kernels.py, test_gpu_optim_kernels.py,
+test_gpu_reduce_window.py): access to the C ABI, and operands as views into NaN-filled parents whose guard
+rows and padding columns must keep their bits. The bound arithmetic is tests/elemwise.py.
 
 The tests call the raw library (`lib()`) with the strides of these views, not the fervit.ops wrappers, so
 that padded strides reach the kernel and a slip in a wrapper cannot hide one in the ABI."""

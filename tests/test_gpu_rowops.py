@@ -586,6 +586,45 @@ def test_colsum(dtype, M, N):
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+@pytest.mark.parametrize("N", [4084, 8192])
+@pytest.mark.parametrize("M", [33, 3001])
+def test_colsum_wide(dtype, M, N):
+    """fer_colsum above 4080 columns: part_reduce_kernel<16> (16 columns x 16 row phases per block; N = 4084:
+    the first width that takes it, the last block with 4 live columns). test_colsum's two forms on randn
+    inputs, and the same two on integer inputs ({-3..3} * 4, integer start values, scale -0.75), where every
+    partial, total and scaled total is exact in fp32 in any order: got == the float64 result."""
+    o = ops()
+    g = torch.Generator().manual_seed(M * 1000 + N)
+    xv, _ = nanview(M, N, 4, tdt(dtype), torch.randn(M, N, generator=g), guard=0)
+    x = xv.float().cpu().double()
+    ref, scale = x.sum(0), x.abs().sum(0)
+    f32 = xv.float().cpu().sum(0)
+    c = measure_c("colsum.wide", dtype, [(f32, ref, scale)])
+    out = torch.full((N + 16,), float("nan"), device=DEV)
+    o.colsum(xv, out[:N])
+    assert_close(f"colsum {dtype}", out[:N], ref, scale, c, 0.0)
+    assert torch.isnan(out[N:]).all().item(), "colsum wrote past its N columns"
+    init = torch.randn(N, generator=g) * 5
+    s = torch.tensor([-0.75], dtype=torch.float32)
+    out = init.to(DEV)
+    o.colsum(xv, out, accumulate=True, scale=s.to(DEV))
+    ref2, scale2 = init.double() + s.double() * ref, init.double().abs() + 0.75 * scale
+    c2 = measure_c("colsum.wide.acc_scale", dtype, [(init + s * f32, ref2, scale2)])
+    assert_close(f"colsum {dtype} accumulate + scale", out, ref2, scale2, c2, 0.0)
+    xi = torch.randint(-3, 4, (M, N), generator=g).float() * 4
+    xiv, _ = nanview(M, N, 4, tdt(dtype), xi, guard=0)
+    refi = xi.double().sum(0)
+    out = torch.full((N + 16,), float("nan"), device=DEV)
+    o.colsum(xiv, out[:N])
+    assert torch.equal(out[:N].cpu().double(), refi), "integer inputs: the column sums are not exact"
+    assert torch.isnan(out[N:]).all().item(), "colsum wrote past its N columns"
+    initi = torch.randint(-5, 6, (N,), generator=g).float()
+    out = initi.to(DEV)
+    o.colsum(xiv, out, accumulate=True, scale=s.to(DEV))
+    assert torch.equal(out.cpu().double(), initi.double() - 0.75 * refi), "integer inputs: accumulate + scale is not exact"
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
 def test_colsum_bad_width_is_an_error(dtype):
     """fer_colsum's host check: N = 6 (no multiple of 4) returns the library's error and writes nothing."""
     o = ops()
