@@ -25,6 +25,16 @@ FER_DEV uint64_t step_seed(uint64_t seed) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
+// A non-dropout draw under the same counter (mixup.hip): the seed mixed with the step, then stream `s` of it by
+// the same finaliser (s takes the counter's place), so related seeds and neighbouring streams share nothing.
+// Kept apart from the dropout call sites, whose table and per-kernel cases are tests/test_gpu_step_seed_kernels.py;
+// a kernel that draws through this helper brings its own counter test (tests/test_gpu_mixup_kernels.py).
+FER_DEV uint64_t step_stream_seed(uint64_t seed, uint64_t s) {
+  uint64_t z = step_seed(seed) ^ (s * 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
 
 namespace fer {
 // host side, per code object

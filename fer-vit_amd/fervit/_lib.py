@@ -139,6 +139,9 @@ SIGNATURES = {
     "fer_latent_dir_draw": (i32, [vp, i64, i32, f32, u64, vp]),
     "fer_label_change": (i32, [fp, i64, fp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "fer_step_advance": (i32, [vp, vp]),
+    "fer_mixup_draw": (i32, [f32, i32, u64, i32, fp, vp, vp]),
+    "fer_mixup_apply": (i32, [fp, vp, fp, fp, i32, i64, vp]),
+    "fer_cross_entropy_mix": (i32, [fp, vp, vp, fp, fp, i32, i32, f32, f32, fp, fp, vp]),
     "fer_transpose_bf16_segments": (i32, [vp, vp, vp, i32, i64, vp]),
     "fer_image_aug_draw": (i32, [fp, i32, i32, vp, u64, vp]),
     "fer_image_augment": (i32, [vp, vp, vp, i32, i32, fp, i32, vp, vp, fp, vp]),

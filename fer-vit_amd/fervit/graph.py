@@ -36,9 +36,11 @@ class StepGraph:
         self.out: Optional[torch.Tensor] = None
         self.counter: Optional[torch.Tensor] = None
 
-    def capture(self) -> "StepGraph":
+    def capture(self, stream: Optional[torch.cuda.Stream] = None) -> "StepGraph":
+        """`stream`: the stream to warm up and capture on (default: a new one) -- the one the caller ran its own
+        eager warm-up steps on, when it passes warmup=0 (train.common.ReplayedTrainEpoch)."""
         dev = torch.device("cuda", torch.cuda.current_device())
-        side = torch.cuda.Stream()
+        side = stream if stream is not None else torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):  # eager warm-up (sizes every workspace)
             for _ in range(self.warmup):

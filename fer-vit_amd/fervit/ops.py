@@ -628,6 +628,53 @@ def cross_entropy(logits, labels, weight=None, label_smoothing=0.0, grad_scale=1
     return loss, dl
 
 
+MIXUP_MAX_B = 2048  # include/fervit.h fer_mixup_draw
+
+
+def mixup_draw(alpha: float, B: int, seed: int, lam: torch.Tensor, perm: torch.Tensor, n_sets: int = 1):
+    """lam [n_sets] fp32 ~ Beta(alpha, alpha) (1 for alpha <= 0) and perm [n_sets * B] int32, drawn on the
+    device from `seed` mixed with the step counter (when one is registered) and the set index."""
+    _dev(lam)
+    if lam.dtype != torch.float32 or perm.dtype != torch.int32 or not (lam.is_contiguous() and perm.is_contiguous()):
+        raise TypeError("mixup_draw: lam is contiguous fp32, perm contiguous int32")
+    if lam.numel() < n_sets or perm.numel() < n_sets * B:
+        raise ValueError("mixup_draw: lam holds n_sets floats, perm n_sets * B indices")
+    check(lib().fer_mixup_draw(float(alpha), B, seed64(seed), n_sets, lam.data_ptr(), perm.data_ptr(), stream()),
+          "mixup_draw")
+    return lam, perm
+
+
+def mixup_apply(x: torch.Tensor, perm: torch.Tensor, lam: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """out[b] = lam * x[b] + (1 - lam) * x[perm[b]] over the rows of a contiguous fp32 batch x [B, ...]; lam is
+    one device float. `out` must not overlap x."""
+    _dev(x)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError("mixup_apply: x is a contiguous fp32 batch")
+    B = x.shape[0]
+    if perm.dtype != torch.int32 or perm.numel() < B or lam.dtype != torch.float32 or lam.numel() < 1:
+        raise TypeError("mixup_apply: perm holds B int32 indices, lam one fp32 value")
+    out = _alloc(out, x)
+    if out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous():
+        raise TypeError("mixup_apply: out has x's shape, dtype and layout")
+    check(lib().fer_mixup_apply(x.data_ptr(), perm.data_ptr(), lam.data_ptr(), out.data_ptr(), B,
+                                x.numel() // max(B, 1), stream()), "mixup_apply")
+    return out
+
+
+def cross_entropy_mix(logits, labels, perm, lam, weight=None, label_smoothing=0.0, grad_scale=1.0, want_grad=True):
+    """lam * CE(logits, labels) + (1 - lam) * CE(logits, labels[perm]) and its dlogits in one launch; perm
+    (int32 [B], None: the identity) and lam (one fp32) are device tensors."""
+    B, Cc = logits.shape
+    if perm is not None and (perm.dtype != torch.int32 or perm.numel() < B):
+        raise TypeError("cross_entropy_mix: perm holds B int32 indices")
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    check(lib().fer_cross_entropy_mix(logits.data_ptr(), labels.data_ptr(), ptr(perm), lam.data_ptr(), ptr(weight), B,
+                                      Cc, label_smoothing, grad_scale, loss.data_ptr(), ptr(dl), stream()),
+          "cross_entropy_mix")
+    return loss, dl
+
+
 def cast_bf16(x, out=None):
     out = _alloc(out, x, dtype=torch.bfloat16)
     check(lib().fer_cast_f32_bf16(x.data_ptr(), out.data_ptr(), x.numel(), stream()), "cast")

@@ -13,6 +13,11 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from fervit import ops
+from fervit._lib import check, lib
+from fervit.graph import StepGraph
+from fervit.loss import MixupCrossEntropyLoss
+from fervit.mixup import DeviceMixup
 from fervit.optim import FusedAdamW, clip_grad_norm_ as fused_clip_grad_norm_
 
 
@@ -120,6 +125,134 @@ def run_train_epoch(model, loader, optimizer, criterion, device, mixup: Optional
     ds = getattr(loader, "dataset", None)
     r = stats.finish(len(ds) if ds is not None else n)
     return r["loss"], r["accuracy"], r["f1_macro"]
+
+
+class ReplayedTrainEpoch:
+    """run_train_epoch's step as one replayed HIP graph (fervit.graph.StepGraph), mixup included: lam and the
+    permutation are drawn on the device (fervit.mixup.DeviceMixup) and the two-target loss reads them there
+    (MixupCrossEntropyLoss), so nothing of the step is decided on the host and every replay draws afresh.
+
+    The step function, on the static input buffers `x`, `y` ([batch_size, ...]):
+        draw -> mix -> zero_grad -> forward -> mixed CE -> backward -> [fused clip] -> FusedAdamW.step
+        -> [no-grad forward on the unmixed batch] -> argmax
+    writing the static `loss` (fp32 scalar) and `pred` (int64 [batch_size]) buffers. The first `warmup` full
+    batches run it eagerly (real training steps, which also size the library workspaces); then it is captured
+    once and replayed for every later full batch, across epochs. A last batch shorter than batch_size runs the
+    same function eagerly on the leading rows of the buffers, behind an eager fer_step_advance (the counter the
+    dropout and mixup seeds and the frozen optimizer's bias correction read). Loss sum and predictions stay on
+    the device; run_epoch reads them once, through EpochStats.finish. close() releases the graph and folds the
+    replays into the optimizer's host step counts.
+
+    `mixup`: None (no mixup) or the Beta parameter (<= 0: lam = 1, as the reference). `criterion`: a
+    CrossEntropyLoss (fervit's or torch's); with mixup its weight and label_smoothing go into a
+    MixupCrossEntropyLoss (or pass one). Unlike run_train_epoch's numpy / CPU draws, the draws here come from
+    fervit's seed stream (fervit.manual_seed)."""
+
+    def __init__(self, model, optimizer, criterion, device, batch_size: int, mixup: Optional[float] = None,
+                 grad_clip=None, metric_forward: bool = False, warmup: int = 2):
+        core = _core(model)
+        if not isinstance(optimizer, FusedAdamW) or optimizer.model is not core or not hasattr(core, "fer_flat"):
+            raise TypeError("ReplayedTrainEpoch needs a FusedAdamW bound to the model (FusedAdamW(..., model=model)): "
+                            "the captured step holds its fused update and device step count")
+        if warmup < 1:
+            raise ValueError("ReplayedTrainEpoch: at least one eager warm-up step sizes the workspaces before capture")
+        if not 1 <= batch_size <= ops.MIXUP_MAX_B:
+            raise ValueError(f"ReplayedTrainEpoch: batch_size outside 1..{ops.MIXUP_MAX_B}")
+        self.model, self.optimizer, self.criterion = model, optimizer, criterion
+        self.device = torch.device(device)
+        self.batch_size, self.grad_clip, self.metric_forward, self.warmup = batch_size, grad_clip, metric_forward, warmup
+        self.mixup = DeviceMixup(mixup, self.device) if mixup is not None else None
+        if self.mixup is None or isinstance(criterion, MixupCrossEntropyLoss):
+            self.mixed_criterion = criterion
+        elif hasattr(criterion, "label_smoothing") and hasattr(criterion, "weight"):
+            self.mixed_criterion = MixupCrossEntropyLoss(criterion.weight, criterion.label_smoothing)
+        else:
+            raise TypeError("ReplayedTrainEpoch: with mixup the criterion is a CrossEntropyLoss (weight, "
+                            "label_smoothing) or a MixupCrossEntropyLoss")
+        self.x: Optional[torch.Tensor] = None
+        self.y = torch.zeros(batch_size, dtype=torch.int64, device=self.device)
+        self.loss = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.pred = torch.zeros(batch_size, dtype=torch.int64, device=self.device)
+        self.logits: Optional[torch.Tensor] = None  # the training logits of the latest step
+        self.graph: Optional[StepGraph] = None
+        self.stream = torch.cuda.Stream(self.device)  # warm-up and capture (its workspaces: StepGraph.capture)
+        self.warm = 0  # eager full-batch steps taken so far
+        self.last: Optional[Dict] = None  # EpochStats.finish of the latest epoch
+
+    def step(self, n: int) -> torch.Tensor:
+        """One training step on the first n rows of the static buffers."""
+        x, y = self.x[:n], self.y[:n]
+        xin = self.mixup.draw(n).mix(x) if self.mixup is not None else x
+        self.optimizer.zero_grad()
+        logits = self.model(xin)
+        loss = self.mixed_criterion(logits, y, self.mixup) if self.mixup is not None else self.criterion(logits, y)
+        loss.backward()
+        if self.grad_clip is not None and self.grad_clip > 0:
+            clip_gradients(self.model, self.optimizer, self.grad_clip)
+        self.optimizer.step()
+        self.logits = logits.detach()
+        if self.metric_forward:
+            with torch.no_grad():
+                self.pred[:n].copy_(self.model(x).argmax(dim=1))
+        else:
+            self.pred[:n].copy_(self.logits.argmax(dim=1))
+        self.loss.copy_(loss.detach())
+        return self.loss
+
+    def load(self, x: torch.Tensor, y: torch.Tensor) -> int:
+        """Copy a batch into the static buffers; returns its size."""
+        n = x.size(0)
+        if n > self.batch_size:
+            raise ValueError(f"ReplayedTrainEpoch: batch of {n} samples, built for {self.batch_size}")
+        if self.x is None:
+            self.x = torch.zeros((self.batch_size, *x.shape[1:]), dtype=torch.float32, device=self.device)
+        self.x[:n].copy_(x, non_blocking=True)
+        self.y[:n].copy_(y, non_blocking=True)
+        return n
+
+    def _run(self, n: int) -> None:
+        if n < self.batch_size:  # the tail: eager, under the captured step's counter when there is one
+            if self.graph is not None:
+                check(lib().fer_step_advance(self.graph.counter.data_ptr(), ops.stream()), "step_advance")
+            self.step(n)
+            return
+        if self.graph is None and self.warm < self.warmup:
+            cur = torch.cuda.current_stream(self.device)
+            self.stream.wait_stream(cur)
+            with torch.cuda.stream(self.stream):
+                self.step(n)
+            cur.wait_stream(self.stream)
+            self.warm += 1
+            return
+        if self.graph is None:
+            self.graph = StepGraph(lambda: self.step(self.batch_size), self.optimizer, warmup=0).capture(self.stream)
+        self.graph.replay()
+
+    def run_epoch(self, loader, on_step=None):
+        """One epoch over `loader`; returns (avg_loss, accuracy, f1_macro) as run_train_epoch does. `on_step(self)`
+        is called after every step has been enqueued (logging, tests): the buffers then hold that step's results
+        in stream order."""
+        self.model.train()
+        stats = EpochStats(self.device)
+        total = 0
+        for x, y in loader:
+            n = self.load(x, y)
+            total += n
+            self._run(n)
+            stats.loss.add_(self.loss, alpha=n)
+            stats.preds.append(self.pred[:n].clone())
+            stats.labels.append(self.y[:n].clone())
+            if on_step is not None:
+                on_step(self)
+        ds = getattr(loader, "dataset", None)
+        self.last = stats.finish(len(ds) if ds is not None else total)
+        return self.last["loss"], self.last["accuracy"], self.last["f1_macro"]
+
+    def close(self) -> None:
+        """Back to eager stepping (StepGraph.release); a later full batch captures again."""
+        if self.graph is not None:
+            self.graph.release()
+            self.graph = None
 
 
 @torch.no_grad()

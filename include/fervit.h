@@ -648,6 +648,35 @@ int fer_image_augment(const uint8_t* src, const int64_t* offsets, const int32_t*
  * first node of the captured step. NULL disables (default). */
 int fer_set_step_counter(const uint64_t* counter);
 int fer_step_advance(uint64_t* counter, fer_stream_t stream);
+
+/* ---- Mixup on the device (csrc/mixup.hip; `train/train_latent_vit_v2.py:118-130`), so that a captured step
+ * draws a new lam and a new permutation on every replay.
+ *
+ * fer_mixup_draw: n_sets independent draws, one workgroup each. Set s draws from the seed mixed with the step
+ * counter above (when set) and then with s; production uses n_sets = 1.
+ *   lam[s]           fp32, Beta(alpha, alpha) for alpha > 0 (not folded to >= 0.5, as the reference), exactly 1
+ *                    for alpha <= 0: g1 / (g1 + g2) of two Gamma(alpha) draws by Marsaglia-Tsang (below 1:
+ *                    Gamma(alpha + 1) U^(1/alpha)), at most 16 attempts each (a draw that exhausts them, chance
+ *                    < 1e-18, takes the proposal's central value)
+ *   perm[s*B + i]    int32, the rank of (hash(perm seed, i), i) among the B pairs, ties on i: a permutation,
+ *                    integers only, reproduced exactly on the host
+ * 1 <= B <= 2048, n_sets >= 1 and both outputs given; anything else returns a negative code and a message.
+ *
+ * fer_mixup_apply: out[b][:] = lam * x[b][:] + (1 - lam) * x[perm[b]][:], fp32 rows of L elements, lam read
+ * from device memory (one float). 16-byte loads and stores when L % 4 == 0 and x and out are 16-byte aligned,
+ * element by element otherwise, same bits. A perm entry outside [0, B) takes the row itself. out must not
+ * overlap x (the gather reads rows an in-place mix would have overwritten); B <= 65535. B <= 0 or L <= 0: no-op.
+ *
+ * fer_cross_entropy_mix: lam * CE(z, y) + (1 - lam) * CE(z, y[perm]) with fer_cross_entropy's semantics per
+ * term (each divided by its own sum w[target]), loss and dlogits = grad_scale * dloss/dlogits in one launch,
+ * one log-sum-exp per row. perm NULL: the identity; dlogits NULL: loss only; B <= 0: no-op. */
+int fer_mixup_draw(float alpha, int B, uint64_t seed, int n_sets, float* lam, int32_t* perm, fer_stream_t stream);
+int fer_mixup_apply(const float* x, const int32_t* perm, const float* lam, float* out, int B, int64_t L,
+                    fer_stream_t stream);
+int fer_cross_entropy_mix(const float* logits, const int64_t* labels, const int32_t* perm, const float* lam,
+                          const float* weight, int B, int C, float label_smoothing, float grad_scale, float* loss,
+                          float* dlogits, fer_stream_t stream);
+
 /* sum of squares of grad (for clip_grad_norm_), out fp32 scalar; ws >= fer_colsum_ws(1, 4096). */
 int fer_sumsq(const float* x, int64_t n, float* out, float* ws, int64_t ws_bytes, fer_stream_t stream);
 /* clip coefficient: coef = min(1, max_norm / (sqrt(sumsq*sq_scale) + 1e-6)) (torch clip_grad_norm_). */
